@@ -4,6 +4,20 @@
 bandwidth against the MI355X HBM roofline and the CPU oracle's
 reference-faithful sweep timed on the host beside it.
 
+A plain run (no --full) does only what the headline figure needs: it builds
+the workload, opens the --chains context, warms up, times the --steps steps,
+writes the outputs if --dump-outputs DIR is given, and prints the result
+line (roofline.achieved from the timed region's wall clock).  --full adds
+every other leg named below: the single-chain context, the cold and rebuild
+calls, the live per-kernel timing (roofline) with the committed PMC traffic,
+the sustained region, the MCMC iterations and the CPU baseline; the --no-*,
+--sustained-s, --mcmc-iters and --cpu-budget options pick among those legs
+and mean nothing without --full.  --dump-outputs DIR writes DIR/field.npy:
+the latent field of every chain (chains x n, float64) as a caller reads it
+(get_field) right after the last timed step; workload, seeds and call
+sequence are fixed by the arguments, so two builds can be compared output
+for output.
+
 Contract: python bench.py --gpus N --steps K --warmup W  (N>1 under
 torch.distributed.run; one rank per GPU).  A step = one chromatic sweep (all K
 colours, all n latents, update_Gaussian.R:257-275 with n_chromatic = 1) of
@@ -227,6 +241,33 @@ def pmc_traffic(chains, n, m, kernel):
     return best
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, groups, n_chains, write=True):
+    """--dump-outputs: the latent field of every chain as a caller of the
+    timed path reads it after the last timed step (get_field of each chain
+    of each (context, chain ids) group) -> out_dir/field.npy, chains x n
+    float64.  Above DUMP_MAX_BYTES a fixed seeded sample of the locations
+    (sorted, the same for every chain) is kept.  Every rank reads (a
+    sharded get_field exchanges first); `write` says which rank stores."""
+    fields = [None] * n_chains
+    for g, ids in groups:
+        for k, i in enumerate(ids):
+            g.select(k)
+            fields[i] = g.get_field()
+        g.select(0)
+    out = np.stack(fields).astype(np.float64, copy=False)
+    keep = DUMP_MAX_BYTES // (8 * n_chains)
+    if out.shape[1] > keep:
+        out = out[:, np.sort(np.random.default_rng(2024).choice(out.shape[1], keep, replace=False))]
+    if write:
+        d = Path(out_dir)
+        d.mkdir(parents=True, exist_ok=True)
+        np.save(d / "field.npy", np.ascontiguousarray(out))
+        log(f"wrote {d / 'field.npy'} {out.shape} float64")
+
+
 def timed_region(run, steps, warmup, dist=None, sync=lambda: None):
     """The bench contract's timed region: `warmup` untimed steps, then exactly
     `steps` steps bracketed by barrier + device sync on both sides; returns
@@ -402,6 +443,8 @@ def shard_main(P, args, world, rank, local_rank, dist, scaling):
         log(f"graph prep {wl['t_graph']:.1f}s colours={info['n_colors']} engine={info['sweep_engine']} "
             f"tiles={info['n_tiles']} owned={info['shard_owned']} exchange_slots={info['shard_exchange_slots']}", rank)
         elapsed, _ = timed_region(run, args.steps, args.warmup, dist, sync)
+        if args.dump_outputs:
+            agree(lambda: dump_outputs(args.dump_outputs, groups, C, write=rank == 0))
     finally:
         for g, _ in groups:
             g.close()
@@ -454,6 +497,13 @@ def main():
     ap.add_argument("--range", type=float, default=0.05)
     ap.add_argument("--n-chromatic", type=int, default=10)
     ap.add_argument("--chains", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: single-chain context, cold and rebuild calls, live per-kernel "
+                         "timing, sustained region, MCMC iterations, CPU baseline (the options below choose "
+                         "among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write DIR/field.npy: every chain's latent field (chains x n "
+                         "float64; a fixed seeded sample of the locations above 64 MB)")
     ap.add_argument("--no-single-chain", action="store_true")
     ap.add_argument("--no-rebuild-calls", action="store_true", help="skip the rebuild-every-call measurement")
     ap.add_argument("--sustained-s", type=float, default=5.0,
@@ -479,6 +529,9 @@ def main():
         args.n, args.m = 10_000_000, 20
         args.multi = "shard-strong"
         args.shard = True
+    if not args.full:  # a plain run: the headline's timed region alone
+        args.no_single_chain = args.no_rebuild_calls = args.no_kernel_timing = args.no_cpu_baseline = True
+        args.sustained_s, args.mcmc_iters = 0.0, 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -581,12 +634,17 @@ def main():
         f"entries={info['n_entries']} engine={info['sweep_engine']} tiles={info['n_tiles']} chunks={info['n_chunks']} "
         f"max_collen={info['max_collen']}", rank)
     elapsed, ctr = timed(ctx, args.steps, args.warmup)
-    el_cold, ctr = timed(ctx, args.steps, args.warmup, cold=True)
-    cold_calls = {"value": args.steps * C * world / el_cold, "unit": "sweeps/s",
-                  "ms_per_step": el_cold * 1e3 / args.steps,
-                  "how": ("beta_0 alternates by 1e-9 between calls (an MCMC iteration's beta_0 Gibbs step): "
-                          "field and factor unchanged, so every call shifts w by -d and r by -d B 1 instead of "
-                          "rebuilding them (NNGP_SWEEP_SHIFT=0: rebuild)")}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if world == 1 else Path(args.dump_outputs) / f"rank{rank}",
+                     [(ctx, list(range(C)))], C)
+    cold_calls = None
+    if args.full:
+        el_cold, ctr = timed(ctx, args.steps, args.warmup, cold=True)
+        cold_calls = {"value": args.steps * C * world / el_cold, "unit": "sweeps/s",
+                      "ms_per_step": el_cold * 1e3 / args.steps,
+                      "how": ("beta_0 alternates by 1e-9 between calls (an MCMC iteration's beta_0 Gibbs step): "
+                              "field and factor unchanged, so every call shifts w by -d and r by -d B 1 instead "
+                              "of rebuilding them (NNGP_SWEEP_SHIFT=0: rebuild)")}
     # per-kernel timing with HIP events on the context's own stream: the
     # sweep kernel's launches alone (tile engine: one persistent launch per
     # call of n_chromatic sweeps; colour engine: one launch per colour)
@@ -596,6 +654,13 @@ def main():
     # row index of an entry shared by the chains of a launch
     bytes_sweep = C * (8 * nnz + 40 * n) + 4 * nnz
     roofline = None
+    if not args.full:
+        # no run of its own: algorithmic bytes over the timed region's wall clock
+        achieved = bytes_sweep * args.steps / elapsed / 1e9
+        roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": None,
+                    "kernel": "whole timed region (wall clock; --full: the sweep kernel's launches alone)",
+                    "algorithmic_bytes_per_sweep": bytes_sweep}
     if not args.no_kernel_timing:
         ksw = nc if engine == 1 else max(4, min(20, args.steps))
         reps = 5 if engine == 1 else 1
@@ -673,7 +738,7 @@ def main():
            "config": {"workload": (f"chromatic sweep n={n} m={args.m} {covfun} range={args.range}, "
                                    f"{C} chains per GPU swept together (value = chain-sweeps/s)"),
                       "n": n, "m": args.m, "n_colors": info["n_colors"], "nnz": nnz, "chains_per_gpu": C,
-                      "n_entries": info["n_entries"], "n_chromatic_per_call": nc,
+                      "n_entries": info["n_entries"], "n_chromatic_per_call": nc, "full": args.full,
                       "sweep_engine": "tiles" if info["sweep_engine"] == 1 else "colours",
                       "n_tiles": info["n_tiles"], "tile_rows_max": info["tile_rows_max"],
                       "n_ghost_cells": info["n_ghost_cells"],
