@@ -1918,7 +1918,11 @@ static int upload_scalars(nngp_ctx* c) {
 
 // A sweep call = prologue (per chain in mask: w = field - beta0 in compact
 // slot order, r = B w at Morton rows; the normals of sweep 0), the colour
-// launches of every sweep, epilogue (field = w + beta0).
+// launches of every sweep, epilogue (field = w + beta0).  Tile engine on one
+// GPU, colours and epilogue enqueued together: the tile launch writes the
+// field itself (TileLaunch::slot_dpos), no epilogue kernel.  The epilogue
+// enqueued alone (sweep_timed's three parts, the shard calls -- a rank also
+// holds other ranks' slots) and the colour engine keep the kernel.
 enum SweepPart { kPrologue = 1, kColours = 2, kEpilogue = 4, kAll = 7 };
 
 static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double* z_dev, int parts = kAll) {
@@ -1935,12 +1939,21 @@ static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double*
     // previous sweep's colour launches; the tile engine draws them inline)
     if (!z_dev && c->engine == 0) HIPCHK(c, launch_normals_compact(c->st, L, mask, 0, n, c->zbuf_d));
   }
+#ifdef NNGP_NO_FUSED_FIELD  // A/B builds: the epilogue kernel on every path
+  const bool fused = false;
+#else
+  const bool fused = (parts & kColours) && (parts & kEpilogue) && c->engine == 1 && !c->shard && n_sweeps > 0;
+#endif
   if ((parts & kColours) && c->engine == 1) {
     TileLaunch a;
     a.n_sweeps = n_sweeps;
     a.chain_mask = mask;
     a.z_in = z_dev;
     a.variant = c->tvariant;
+    if (fused) {
+      a.slot_dpos = c->slot_dpos_d;
+      a.field = fp;
+    }
     if (c->tcs) {
       a.stagger = c->tstagger;
       HIPCHK(c, launch_sweep_tiles_cs(c->st, tile_dev(c), a, c->tl.max_rows, c->tl.NTK, c->tl.max_batches,
@@ -1969,7 +1982,7 @@ static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double*
       }
     }
   }
-  if (parts & kEpilogue)
+  if ((parts & kEpilogue) && !fused)
     HIPCHK(c, launch_slots_to_field_multi(c->st, c->n, c->slot_dpos_d, fp, c->scal_d, c->w_slot_d, c->C, mask));
   return NNGP_OK;
 }

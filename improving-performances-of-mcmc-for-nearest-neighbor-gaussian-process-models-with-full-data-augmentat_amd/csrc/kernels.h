@@ -245,6 +245,14 @@ struct TileLaunch {
   const double* z_in;         // injected normals, per sweep: slot x C (nullptr: Philox inline)
   int stagger = 0;            // chain-split: chain k starts k x stagger ticks (100 MHz) late
   int variant = 0;            // NNGP_TILE_VARIANT: experiment bits (probe builds only)
+  // the call's field write fused into the launch (one GPU: every slot is some
+  // tile's own): each tile ends with field[ch][slot_dpos[x]] = w_slot + beta_0
+  // over its own slots x, for the chains in chain_mask -- what
+  // slots_to_field_multi_kernel computes, without the pass of its own.
+  // slot_dpos == nullptr: the launch leaves the fields alone.  (The field
+  // buffers live as long as the context, so a captured graph may hold them.)
+  const int* slot_dpos = nullptr;
+  FieldPtrs field = {};
 };
 
 // cells per thread of an own batch (the layout's RMAX): two batches of C

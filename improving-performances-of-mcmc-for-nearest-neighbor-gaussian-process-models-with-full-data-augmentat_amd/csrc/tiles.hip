@@ -225,15 +225,13 @@ __device__ __forceinline__ void tile_load_cells(const TileDev& D, const int4 B, 
 #pragma unroll
       for (int ch = 0; ch < C; ++ch) b.v[j][ch] = __builtin_nontemporal_load(D.cell_val + ch * D.n_cells + e);
     } else {
-      // padding (device encoding, tile_lr); where the products run whole
-      // groups of cells (tile_products: wave-local batches) with a
-      // zero value, so that a cell past R is a no-op there (the tile's last
-      // row times 0)
+      // padding (device encoding, tile_lr) with a zero value: where the
+      // products run whole groups of cells (tile_products: wave-local
+      // batches) a cell past R is a no-op (the tile's last row times 0), and
+      // no instantiation leaves a cell register uninitialised
       b.pk[j] = 0u;
-      if constexpr (NT == 64) {
 #pragma unroll
-        for (int ch = 0; ch < C; ++ch) b.v[j][ch] = 0.0;
-      }
+      for (int ch = 0; ch < C; ++ch) b.v[j][ch] = 0.0;
     }
   }
 }
@@ -277,6 +275,32 @@ __device__ __forceinline__ void tile_prep_items(const TileDev& D, const TileLaun
   }
 }
 
+// r of the tile's local rows: the index of (local row lr, chain ch) -- the
+// one place that knows the layout; every access to the tile's r goes through it.
+//  CM = 0, interleaved: lr * C + ch.  The layout of r in global memory (RG
+//    tiles and the r the calls hand on: a row's chains share a line).  In LDS
+//    the compiler reads a row of 3 chains as one paired 2 x 8-byte read
+//    (chains 0, 1) plus a single one (chain 2).
+//  CM = 1, chain-major (LDS only): ch * RS + lr with RS >= the tile's rows.
+//    RS is a per-tile runtime value (uniform: a scalar register), so the
+//    chains' accesses cannot be paired: each is a single 8-byte read or write
+//    at the row address plus one transient add, and the row address stays the
+//    one live register it is in the interleaved form.  r takes RS x C doubles.
+// C = 1: the two coincide.
+constexpr int tile_r_chain_major(int C, int RG, int SH, int XW) {
+#ifdef NNGP_TILE_R_INTERLEAVED  // A/B builds: the interleaved layout everywhere
+  return 0;
+#else
+  // the wave-local 3-chain kernel (the headline instantiation); the other
+  // instantiations keep the interleaved layout until an A/B of their own
+  return C == 3 && !RG && !SH && XW == 2;
+#endif
+}
+template <int C, int CM>
+__device__ __forceinline__ int tile_r_index(int lr, int ch, int RS) {
+  return CM ? ch * RS + lr : lr * C + ch;
+}
+
 // ghost cells of one chunk: local row, foreign slot, B values
 template <int C, int GMAX>
 struct TileGhostRegs {
@@ -304,12 +328,13 @@ __device__ __forceinline__ void tile_load_ghosts(const TileDev& D, int gb, int g
 // distinct (one foreign member per colour per row), so every read goes out
 // before any write (see tile_own_scatter)
 struct TileState;
-template <int C, int GMAX>
+template <int C, int GMAX, int CM = 0>
 __device__ __forceinline__ void tile_ghost_adds(TileState& S, const TileGhostRegs<C, GMAX>& gr);
 
 // per-workgroup state of the persistent sweep
 struct TileState {
   double* r_s;
+  int RS;         // chain stride of r_s in the chain-major layout (tile_r_index)
   double* acc_s;
   double* wsum;
   double* sc_s;   // C x {inv_s2, inv_t2}
@@ -335,7 +360,7 @@ struct TileState {
   unsigned long long tp[8], t_prev;
 };
 
-template <int C, int GMAX>
+template <int C, int GMAX, int CM>
 __device__ __forceinline__ void tile_ghost_adds(TileState& S, const TileGhostRegs<C, GMAX>& gr) {
   double rv[GMAX][C], dv[GMAX][C];
 #pragma unroll
@@ -344,7 +369,7 @@ __device__ __forceinline__ void tile_ghost_adds(TileState& S, const TileGhostReg
     const int row = ok ? gr.lr[k] : 0, x = ok ? gr.gx[k] : 0;
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {
-      rv[k][ch] = S.r_s[row * C + ch];
+      rv[k][ch] = S.r_s[tile_r_index<C, CM>(row, ch, S.RS)];
       dv[k][ch] = S.gdw_s[x * C + ch];
     }
   }
@@ -352,7 +377,7 @@ __device__ __forceinline__ void tile_ghost_adds(TileState& S, const TileGhostReg
   for (int k = 0; k < GMAX; ++k)
     if (gr.lr[k] >= 0)
 #pragma unroll
-      for (int ch = 0; ch < C; ++ch) S.r_s[gr.lr[k] * C + ch] = rv[k][ch] + gr.gv[k][ch] * dv[k][ch];
+      for (int ch = 0; ch < C; ++ch) S.r_s[tile_r_index<C, CM>(gr.lr[k], ch, S.RS)] = rv[k][ch] + gr.gv[k][ch] * dv[k][ch];
 }
 
 #define TSTAMP(S, k)                                                      \
@@ -415,8 +440,8 @@ constexpr int kOwnDrawBarriers = 3;
 // the last group runs whole; padding reads the tile's last row.  Wave-local
 // batches only (tile_own_wl); tile_own_draw keeps its cell-by-cell loop (the
 // group's registers spill its 2-chain instantiation)
-template <int C, int RMAX, int GRP, class TB>
-__device__ __forceinline__ void tile_products(const TB& b, int R, const double* __restrict__ r_s,
+template <int C, int RMAX, int GRP, int CM, class TB>
+__device__ __forceinline__ void tile_products(const TB& b, int R, const double* __restrict__ r_s, int RS,
                                               double* __restrict__ acc_s, uint32_t lrmax, double (&run)[C],
                                               int& cont_q, bool& seen_start) {
 #pragma unroll
@@ -430,7 +455,7 @@ __device__ __forceinline__ void tile_products(const TB& b, int R, const double* 
       if (j0 + jj < RMAX) {
         const uint32_t lr = min(tile_lr(b.pk[j0 + jj]), lrmax);
 #pragma unroll
-        for (int ch = 0; ch < C; ++ch) rv[jj][ch] = r_s[lr * C + ch];
+        for (int ch = 0; ch < C; ++ch) rv[jj][ch] = r_s[tile_r_index<C, CM>((int)lr, ch, RS)];
       }
     }
 #pragma unroll
@@ -486,7 +511,7 @@ __device__ __forceinline__ void tile_own_draw(const TileDev& D, const TileLaunch
       const bool st = (pk & kTStart) != 0;
       const double keep = st ? 0.0 : 1.0;  // restart at a slot start: run * 0 + p (see seg_scan_step)
 #pragma unroll
-      for (int ch = 0; ch < C; ++ch) run[ch] = __builtin_fma(run[ch], keep, b.v[j][ch] * r_s[lr * C + ch]);
+      for (int ch = 0; ch < C; ++ch) run[ch] = __builtin_fma(run[ch], keep, b.v[j][ch] * r_s[tile_r_index<C, 0>((int)lr, ch, 0)]);
       const int q = (int)((pk >> kTileQShift) & kTileQMask);
       if (pk & kTEnd) {
 #pragma unroll
@@ -578,7 +603,7 @@ __device__ __forceinline__ void tile_own_draw(const TileDev& D, const TileLaunch
 // so the reads of r and dw of a group of rows all go out before any write:
 // one LDS round trip per group instead of one per cell (the compiler cannot
 // see the distinctness and would order every read after the previous write)
-template <int C, int NT, int RMAX, int PROBE>
+template <int C, int NT, int RMAX, int PROBE, int CM = 0>
 __device__ __forceinline__ void tile_own_scatter(TileState& S, const TileBatchRegs<C, NT, RMAX>& b, int R,
                                                  const double* acc_base = nullptr) {
   constexpr int GRP = RMAX < 4 ? RMAX : 4;  // rows per group (registers: 2 x GRP x C doubles)
@@ -596,7 +621,7 @@ __device__ __forceinline__ void tile_own_scatter(TileState& S, const TileBatchRe
       const int row = ok ? (int)lr : 0, q = ok ? (int)((b.pk[j] >> kTileQShift) & kTileQMask) : 0;
 #pragma unroll
       for (int ch = 0; ch < C; ++ch) {
-        rv[jj][ch] = r_s[row * C + ch];
+        rv[jj][ch] = r_s[tile_r_index<C, CM>(row, ch, S.RS)];
         dv[jj][ch] = acc_s[q * C + ch];
       }
     }
@@ -606,7 +631,7 @@ __device__ __forceinline__ void tile_own_scatter(TileState& S, const TileBatchRe
       const uint32_t lr = tile_lr(b.pk[j]);
       if (j < R && lr != kTPad) {
 #pragma unroll
-        for (int ch = 0; ch < C; ++ch) r_s[lr * C + ch] = rv[jj][ch] + b.v[j][ch] * dv[jj][ch];
+        for (int ch = 0; ch < C; ++ch) r_s[tile_r_index<C, CM>((int)lr, ch, S.RS)] = rv[jj][ch] + b.v[j][ch] * dv[jj][ch];
       }
     }
   }
@@ -896,7 +921,7 @@ __device__ __forceinline__ void tile_phase_ib(const TileDev& D, const TileLaunch
 // complete in issue order; wave_lds_order keeps the compiler from moving them.
 __device__ __forceinline__ void wave_lds_order() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-template <int C, int RMAX, int PROBE, int SH>
+template <int C, int RMAX, int PROBE, int SH, int CM>
 __device__ __forceinline__ void tile_own_wl(const TileDev& D, const TileLaunch& a, const TileShard& sh, TileState& S,
                                             TileBatchRegs<C, 64, RMAX>& b, unsigned epoch, double* acc_w,
                                             bool first = false) {
@@ -917,7 +942,7 @@ __device__ __forceinline__ void tile_own_wl(const TileDev& D, const TileLaunch& 
   double run[C];
   int cont_q = -1;
   bool seen_start = false;
-  tile_products<C, RMAX, 4>(b, R, r_s, acc_s, S.lrmax, run, cont_q, seen_start);
+  tile_products<C, RMAX, 4, CM>(b, R, r_s, S.RS, acc_s, S.lrmax, run, cont_q, seen_start);
   // segmented inclusive scan of the lane tails inside the wave (as
   // tile_own_draw's); lane 0 holds the first cell of the wave's first slot,
   // so nothing is carried in from another wave
@@ -977,7 +1002,7 @@ __device__ __forceinline__ void tile_own_wl(const TileDev& D, const TileLaunch& 
 // register sets): the wave's next batch loads at the phase start, its HBM
 // stream overlapping this colour's work; otherwise its records after the
 // draw and its cells after the scatter and the draw preparation.
-template <int C, int NT, int RMAX, int GMAX, int PROBE, int SH, int DB>
+template <int C, int NT, int RMAX, int GMAX, int PROBE, int SH, int DB, int CM>
 __device__ __forceinline__ void tile_phase_wl(const TileDev& D, const TileLaunch& a, const TileShard& sh,
                                               TileState& S, int ph, TileBatchRegs<C, 64, RMAX>& cur,
                                               TileBatchRegs<C, 64, RMAX>& nxt, TileGhostRegs<C, GMAX>& gr) {
@@ -1001,7 +1026,7 @@ __device__ __forceinline__ void tile_phase_wl(const TileDev& D, const TileLaunch
       tile_load_batch<C, 64, RMAX, SH>(D, S.batch_s[bi], cur, lane);
       tile_prep_items<C, 64, RMAX>(D, a, S.sc_s, S.seed_s, s, cur, lane);
     }
-    tile_own_wl<C, RMAX, PROBE, SH>(D, a, sh, S, cur, epoch, acc_w, bi == bfirst);
+    tile_own_wl<C, RMAX, PROBE, SH, CM>(D, a, sh, S, cur, epoch, acc_w, bi == bfirst);
     if (bi == bfirst && S.wv == 0 && lane == 0)  // the exchange wave's poll gate (tile_phase_xw)
       __hip_atomic_store(S.pub_s, ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     const int R = cur.R;
@@ -1009,7 +1034,7 @@ __device__ __forceinline__ void tile_phase_wl(const TileDev& D, const TileLaunch
       if (!DB && more) tile_load_items<C, 64, RMAX, SH>(D, S.batch_s[bnext], nxt, lane);
       if (g1 > g0) tile_load_ghosts<C, NT, GMAX>(D, g0, g1, gr, t);
     }
-    tile_own_scatter<C, 64, RMAX, PROBE>(S, cur, R, acc_w);
+    tile_own_scatter<C, 64, RMAX, PROBE, CM>(S, cur, R, acc_w);
   }
   if (bfirst >= bend) {  // no batch of this colour for this wave
     if (!DB && more) tile_load_items<C, 64, RMAX, SH>(D, S.batch_s[bnext], nxt, lane);
@@ -1023,7 +1048,7 @@ __device__ __forceinline__ void tile_phase_wl(const TileDev& D, const TileLaunch
   TLSTAMP(S, 2);
   for (int gb = g0; gb < g1; gb += NT * GMAX) {
     if (gb != g0) tile_load_ghosts<C, NT, GMAX>(D, gb, g1, gr, t);
-    tile_ghost_adds<C, GMAX>(S, gr);
+    tile_ghost_adds<C, GMAX, CM>(S, gr);
   }
   __syncthreads();
   TLSTAMP(S, 3);
@@ -1048,7 +1073,7 @@ __device__ __forceinline__ int tile_wlib_first(const TileState& S, int c) {
   return fi < S.bsp_s[c] ? fi : (fb < S.bptr_s[c + 1] ? fb : -1);
 }
 
-template <int C, int NT, int RMAX, int GMAX, int PROBE, int SH>
+template <int C, int NT, int RMAX, int GMAX, int PROBE, int SH, int CM>
 __device__ __forceinline__ void tile_phase_wlib(const TileDev& D, const TileLaunch& a, const TileShard& sh,
                                                 TileState& S, int ph, TileBatchRegs<C, 64, RMAX>& cur,
                                                 TileGhostRegs<C, GMAX>& gr) {
@@ -1075,7 +1100,7 @@ __device__ __forceinline__ void tile_phase_wlib(const TileDev& D, const TileLaun
       tile_load_batch<C, 64, RMAX, SH>(D, S.batch_s[bi], cur, lane);
       tile_prep_items<C, 64, RMAX>(D, a, S.sc_s, S.seed_s, s, cur, lane);
     }
-    tile_own_wl<C, RMAX, PROBE, SH>(D, a, sh, S, cur, epoch, acc_w);
+    tile_own_wl<C, RMAX, PROBE, SH, CM>(D, a, sh, S, cur, epoch, acc_w);
     const int R = cur.R;
     if (bi + W >= bsp) {  // the last interior batch: its records are dead
       if (bfirst < b1) {
@@ -1086,7 +1111,7 @@ __device__ __forceinline__ void tile_phase_wlib(const TileDev& D, const TileLaun
       }
       if (g1 > g0) tile_load_ghosts<C, NT, GMAX>(D, g0, g1, gr, t);
     }
-    tile_own_scatter<C, 64, RMAX, PROBE>(S, cur, R, acc_w);
+    tile_own_scatter<C, 64, RMAX, PROBE, CM>(S, cur, R, acc_w);
   }
   if (ifirst >= bsp) {  // no interior batch: cur already holds the first boundary batch, if any
     if (g1 > g0) tile_load_ghosts<C, NT, GMAX>(D, g0, g1, gr, t);
@@ -1099,7 +1124,7 @@ __device__ __forceinline__ void tile_phase_wlib(const TileDev& D, const TileLaun
   TLSTAMP(S, 4);
   for (int gb = g0; gb < g1; gb += NT * GMAX) {
     if (gb != g0) tile_load_ghosts<C, NT, GMAX>(D, gb, g1, gr, t);
-    tile_ghost_adds<C, GMAX>(S, gr);
+    tile_ghost_adds<C, GMAX, CM>(S, gr);
   }
   __syncthreads();  // B
   TLSTAMP(S, 2);
@@ -1109,13 +1134,13 @@ __device__ __forceinline__ void tile_phase_wlib(const TileDev& D, const TileLaun
       tile_load_batch<C, 64, RMAX, SH>(D, S.batch_s[bi], cur, lane);
       tile_prep_items<C, 64, RMAX>(D, a, S.sc_s, S.seed_s, s, cur, lane);
     }
-    tile_own_wl<C, RMAX, PROBE, SH>(D, a, sh, S, cur, epoch, acc_w);
+    tile_own_wl<C, RMAX, PROBE, SH, CM>(D, a, sh, S, cur, epoch, acc_w);
     const int R = cur.R;
     if (bi + W >= b1 && nxt_b >= 0) {
       tile_load_items<C, 64, RMAX, SH>(D, S.batch_s[nxt_b], cur, lane);
       nx_items = true;
     }
-    tile_own_scatter<C, 64, RMAX, PROBE>(S, cur, R, acc_w);
+    tile_own_scatter<C, 64, RMAX, PROBE, CM>(S, cur, R, acc_w);
   }
   if (nxt_b >= 0) {
     if (!nx_items) tile_load_items<C, 64, RMAX, SH>(D, S.batch_s[nxt_b], cur, lane);
@@ -1148,7 +1173,7 @@ __device__ __forceinline__ void tile_phase_wlib(const TileDev& D, const TileLaun
 // LAG (interior-first wave-local tiles): phase ph hands off colour ph - 1
 // between its interior and boundary batches (none at ph = 0; ph = nph: the
 // launch's epilogue)
-template <int C, int NT, int GMAX, int PROBE, int SH, int WL = 0, int LAG = 0>
+template <int C, int NT, int GMAX, int PROBE, int SH, int WL = 0, int LAG = 0, int CM = 0>
 __device__ __forceinline__ void tile_phase_xw(const TileDev& D, TileState& S, int ph, TileGhostRegs<C, GMAX>& gr) {
   constexpr int PB = 4;  // granule polls in flight per lane
   const int K = S.K, t = S.t, lane = S.lane;
@@ -1246,7 +1271,7 @@ __device__ __forceinline__ void tile_phase_xw(const TileDev& D, TileState& S, in
   __syncthreads();
   for (int gb = g0; gb < g1; gb += NT * GMAX) {
     if (gb != g0) tile_load_ghosts<C, NT, GMAX>(D, gb, g1, gr, t);
-    tile_ghost_adds<C, GMAX>(S, gr);
+    tile_ghost_adds<C, GMAX, CM>(S, gr);
   }
   __syncthreads();
   if (LAG && ph < S.nph) __syncthreads();  // C: the cell waves' boundary batches are done
@@ -1326,11 +1351,13 @@ __device__ __forceinline__ void tile_phase_cells(const TileDev& D, const TileLau
 // its CU and each one's stream and hand-off waits overlap the others' work.
 // Chain-major numbering: the dispatcher places chain 0's tiles first, so a
 // chain never waits on a tile of its own that is not resident.
+constexpr int kTailU = 4;  // slots / rows per thread and pass of the closing write-backs
 template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int RG, int IB, int CS, int XW = 0>
 __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a, const TileShard& sh) {
   static_assert(!XW || ((!RG || XW == 2) && (!IB || XW == 2) && CS == C),
                 "exchange-wave tiles: joint chains; split layouts and r in global memory only with wave-local batches");
   constexpr int NTC = XW ? NT - 64 : NT;  // cell threads
+  constexpr int CM = CS == C ? tile_r_chain_major(C, RG, SH, XW) : 0;  // r_s layout (tile_r_index)
   using BR = TileBatchRegs<C, NTC, RMAX>;
   constexpr int NW = NT / 64;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1366,6 +1393,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
   S.lrmax = nrows > 0 ? (uint32_t)(nrows - 1) : 0u;
   const int b_lo = D.batch_ptr[T * K], nbt = D.batch_ptr[T * K + K] - b_lo;
   S.r_s = RG ? D.rg + (size_t)row0 * C : smem;
+  S.RS = nrows;  // chain-major: no padding, r takes nrows x C doubles in either layout
   S.acc_s = RG ? smem : smem + ((nrows * C + 1) / 2) * 2;  // kAccSlots x C: slot totals, then dw
   S.wsum = S.acc_s + kAccSlots * C;              // NW x C: segmented wave totals
   S.sc_s = S.wsum + NW * C;                      // C x {inv_s2, inv_t2}
@@ -1395,7 +1423,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {
       const double v = D.r[g + ch];
-      S.r_s[lr * C + ch] = dsh[ch] != 0.0 ? __builtin_fma(-dsh[ch], D.b1[ch][row], v) : v;
+      S.r_s[tile_r_index<C, CM>(lr, ch, S.RS)] = dsh[ch] != 0.0 ? __builtin_fma(-dsh[ch], D.b1[ch][row], v) : v;
     }
   }
   // per-tile metadata in LDS: no dependent scalar loads in the phase loop
@@ -1434,9 +1462,9 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
       TileGhostRegs<C, GMAX> GX;
       __syncthreads();
       if constexpr (IB) {
-        for (int ph = 0; ph <= S.nph; ++ph) tile_phase_xw<C, NT, GMAX, PROBE, SH, 1, 1>(D, S, ph, GX);
+        for (int ph = 0; ph <= S.nph; ++ph) tile_phase_xw<C, NT, GMAX, PROBE, SH, 1, 1, CM>(D, S, ph, GX);
       } else {
-        for (int ph = 0; ph < S.nph; ++ph) tile_phase_xw<C, NT, GMAX, PROBE, SH, XW == 2>(D, S, ph, GX);
+        for (int ph = 0; ph < S.nph; ++ph) tile_phase_xw<C, NT, GMAX, PROBE, SH, XW == 2, 0, CM>(D, S, ph, GX);
       }
     } else if constexpr (XW == 2 && IB) {  // interior-first wave-local batches
       TileBatchRegs<C, 64, RMAX> A;
@@ -1447,7 +1475,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
         tile_prep_items<C, 64, RMAX>(D, a, S.sc_s, S.seed_s, 0, A, S.lane);
       }
       __syncthreads();
-      for (int ph = 0; ph < S.nph; ++ph) tile_phase_wlib<C, NT, RMAX, GMAX, PROBE, SH>(D, a, sh, S, ph, A, GA);
+      for (int ph = 0; ph < S.nph; ++ph) tile_phase_wlib<C, NT, RMAX, GMAX, PROBE, SH, CM>(D, a, sh, S, ph, A, GA);
       // epilogue: the hand-off of the call's last colour (the exchange wave's ph = nph)
       const int cp = S.nph > 0 ? (S.nph - 1) % K : 0;
       const int g0 = S.gptr_s[cp], g1 = S.nph > 0 ? S.gptr_s[cp + 1] : g0;
@@ -1456,7 +1484,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
         __syncthreads();
         for (int gb = g0; gb < g1; gb += NT * GMAX) {
           if (gb != g0) tile_load_ghosts<C, NT, GMAX>(D, gb, g1, GA, t);
-          tile_ghost_adds<C, GMAX>(S, GA);
+          tile_ghost_adds<C, GMAX, CM>(S, GA);
         }
         __syncthreads();
       } else {
@@ -1473,11 +1501,11 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
       __syncthreads();
       if (DB) {
         for (int ph = 0; ph < S.nph; ph += 2) {
-          tile_phase_wl<C, NT, RMAX, GMAX, PROBE, SH, DB>(D, a, sh, S, ph, A, B, GA);
-          if (ph + 1 < S.nph) tile_phase_wl<C, NT, RMAX, GMAX, PROBE, SH, DB>(D, a, sh, S, ph + 1, B, A, GA);
+          tile_phase_wl<C, NT, RMAX, GMAX, PROBE, SH, DB, CM>(D, a, sh, S, ph, A, B, GA);
+          if (ph + 1 < S.nph) tile_phase_wl<C, NT, RMAX, GMAX, PROBE, SH, DB, CM>(D, a, sh, S, ph + 1, B, A, GA);
         }
       } else {
-        for (int ph = 0; ph < S.nph; ++ph) tile_phase_wl<C, NT, RMAX, GMAX, PROBE, SH, DB>(D, a, sh, S, ph, A, A, GA);
+        for (int ph = 0; ph < S.nph; ++ph) tile_phase_wl<C, NT, RMAX, GMAX, PROBE, SH, DB, CM>(D, a, sh, S, ph, A, A, GA);
       }
     } else {
       BR A, B;
@@ -1530,10 +1558,59 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
   // order from the same start, so the copies written by different tiles are
   // bitwise equal.
   __syncthreads();
-  for (int lr = t; lr < nrows; lr += NT) {
-    double* rg = const_cast<double*>(D.r) + (size_t)D.erow[row0 + lr] * CS;
+  // the call's field write (TileLaunch::slot_dpos): field = w + beta_0 of the
+  // tile's own slots -- the contiguous range the shifted prologue walks, whose
+  // w_slot values this workgroup stored itself (ordered by the barrier) --
+  // into location order, for the chains of the mask only.  The same add as
+  // slots_to_field_multi_kernel's: bitwise the same field.
+  if (a.slot_dpos && nbt > 0) {
+    double* fld[C];
+    double b0[C];
 #pragma unroll
-    for (int ch = 0; ch < C; ++ch) rg[ch] = S.r_s[lr * C + ch];
+    for (int ch = 0; ch < C; ++ch) {
+      if constexpr (CS == C) {
+        fld[ch] = a.field.p[ch];
+      } else {  // chain-split (C == 1): this workgroup's chain
+        static_assert(kMaxChains == 4, "the chain's field pointer is picked by selects");
+        fld[ch] = ch0 == 0 ? a.field.p[0] : ch0 == 1 ? a.field.p[1] : ch0 == 2 ? a.field.p[2] : a.field.p[3];
+      }
+      b0[ch] = D.scal[ch].beta0;
+    }
+    const int x0 = S.batch_s[0].w, x1 = S.batch_s[nbt - 1].w + S.batch_s[nbt - 1].z;
+    // kTailU slots per thread and pass: every load of a pass goes out before
+    // its first store (the compiler cannot move a load over a store that may
+    // alias it, and a load per store would put a memory round trip between
+    // any two stores of a thread)
+    for (int x = x0 + t; x < x1; x += NT * kTailU) {
+      int d[kTailU];
+      double w[kTailU][C];
+#pragma unroll
+      for (int u = 0; u < kTailU; ++u) {
+        const int xs = x + u * NT;
+        d[u] = xs < x1 ? a.slot_dpos[xs] : -1;
+#pragma unroll
+        for (int ch = 0; ch < C; ++ch)
+          w[u][ch] = (xs < x1 && ((a.chain_mask >> ch) & 1)) ? D.w_slot[(size_t)xs * CS + ch] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < kTailU; ++u)
+        if (d[u] >= 0)
+#pragma unroll
+          for (int ch = 0; ch < C; ++ch)
+            if ((a.chain_mask >> ch) & 1) fld[ch][d[u]] = w[u][ch] + b0[ch];
+    }
+  }
+  for (int lr = t; lr < nrows; lr += NT * kTailU) {  // (passes as above)
+    int row[kTailU];
+#pragma unroll
+    for (int u = 0; u < kTailU; ++u) row[u] = lr + u * NT < nrows ? D.erow[row0 + lr + u * NT] : -1;
+#pragma unroll
+    for (int u = 0; u < kTailU; ++u) {
+      if (row[u] < 0) continue;
+      double* rg = const_cast<double*>(D.r) + (size_t)row[u] * CS;
+#pragma unroll
+      for (int ch = 0; ch < C; ++ch) rg[ch] = S.r_s[tile_r_index<C, CM>(lr + u * NT, ch, S.RS)];
+    }
   }
   if (PROBE == 1 && t == 0) {
     unsigned long long* o = D.dbg + (size_t)T * 8;
