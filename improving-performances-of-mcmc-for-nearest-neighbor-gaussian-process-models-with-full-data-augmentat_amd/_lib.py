@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "nngp_factor_chains", "nngp_loglik_chains", "nngp_field_response_ratio_chains",
     "nngp_sum_squared_residuals_chains", "nngp_loglik_pair_chains",
     "nngp_ancillary_step_chains", "nngp_sufficient_step_chains",
+    "nngp_summary", "nngp_summary_stats",
 )
 SHARD_ID_BYTES = 128  # NNGP_SHARD_ID_BYTES
 IPC_HANDLE_BYTES = 192  # NNGP_IPC_HANDLE_BYTES
@@ -141,6 +142,10 @@ def _load():
     L.nngp_record_field.argtypes = [_vp, C.c_int]
     L.nngp_get_records.argtypes = [_vp, C.c_int, C.c_int, _dp]
     L.nngp_records_stream.argtypes = [_vp, _vp, C.c_int]
+    L.nngp_summary.argtypes = [C.c_int, C.POINTER(_vp), C.POINTER(C.c_longlong), C.c_int, C.c_longlong, _vp,
+                               C.c_int, _dp]
+    L.nngp_summary_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong),
+                                     C.POINTER(C.c_int)]
     return L
 
 

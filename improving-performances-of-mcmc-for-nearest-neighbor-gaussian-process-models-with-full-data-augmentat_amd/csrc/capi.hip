@@ -21,6 +21,7 @@
 #include "graph_prep.h"
 #include "kernels.h"
 #include "rec_stream.h"
+#include "summary.h"
 
 using namespace nngp;
 
@@ -256,6 +257,7 @@ constexpr int kTileNT = 512;       // threads per tile workgroup (NNGP_TILE_NT: 
 constexpr int kTileTarget = 2048;  // locations per tile (default tile count: n / this, <= CUs)
 
 thread_local std::string g_err;
+thread_local SummaryStats g_summary_stats;  // of this thread's last successful nngp_summary
 
 int fail_hip(nngp_ctx* c, hipError_t e, const char* what) {
   std::string m = std::string(what) + ": " + hipGetErrorString(e);
@@ -3145,6 +3147,23 @@ int nngp_device_normals(int device, uint64_t seed, uint64_t sweep, int n, double
   if (e == hipSuccess) e = hipMemcpy(z, d, sizeof(double) * n, hipMemcpyDeviceToHost);
   hipFree(d);
   return e == hipSuccess ? NNGP_OK : fail_hip(nullptr, e, "device_normals");
+}
+
+// ---------------------------------------------------------------- summaries
+int nngp_summary(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
+                 const double* row_offset, int chunk_cols, double* out) {
+  std::string err;
+  const int st = summary_run(device, blocks, block_rows, n_blocks, n, row_offset, chunk_cols, out, &g_summary_stats, err);
+  return st == NNGP_OK ? NNGP_OK : fail_msg(nullptr, st, err);
+}
+
+int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols) {
+  if (g_summary_stats.n_chunks < 1) return fail_msg(nullptr, NNGP_ERR_STATE, "summary_stats: no summary on this thread yet");
+  if (copy_ms) *copy_ms = g_summary_stats.copy_ms;
+  if (kernel_ms) *kernel_ms = g_summary_stats.kernel_ms;
+  if (staged_bytes) *staged_bytes = g_summary_stats.staged_bytes;
+  if (chunk_cols) *chunk_cols = g_summary_stats.chunk_cols;
+  return NNGP_OK;
 }
 
 }  // extern "C"

@@ -11,8 +11,25 @@ def _quantile7(x, q):
     return np.quantile(x, q, axis=0)  # numpy 'linear' == R type 7
 
 
-def get_summary(samples):
-    """estimate.R:1-6: mean, q0.025, median, q0.975, sd per column."""
+def get_summary(samples, backend="host", device=-1, row_offset=None, chunk_cols=0):
+    """estimate.R:1-6: mean, q0.025, median, q0.975, sd per column.
+
+    ``samples``: a 2-D array (rows = samples) or a list of 2-D arrays with equal
+    column counts, summarised as their row-wise stack; ``row_offset`` (one
+    value per row of the stack) is subtracted from its row first.
+    ``backend="host"`` (default) is numpy; ``backend="hip"`` runs the selection
+    kernel of libnngp.so (nngp_summary) on ``device``: float64 row-contiguous
+    blocks are passed where they lie, any other block is copied (only that
+    block), and ``chunk_cols`` columns are staged per launch (0: automatic).
+    Returns an (n, 5) array."""
+    if backend == "hip":
+        return _summary_hip(samples, device, row_offset, chunk_cols)
+    if backend != "host":
+        raise ValueError(f"get_summary: backend must be 'host' or 'hip', not {backend!r}")
+    if isinstance(samples, (list, tuple)) and len(samples) and np.ndim(samples[0]) == 2:
+        samples = np.vstack([np.asarray(b, np.float64) for b in samples])
+    if row_offset is not None:
+        samples = np.asarray(samples, np.float64) - np.asarray(row_offset, np.float64).reshape(-1, 1)
     s = np.atleast_2d(np.asarray(samples, np.float64))
     if s.shape[0] == 1 and s.ndim == 2 and s.shape[1] > 1 and np.asarray(samples).ndim == 1:
         s = s.T
@@ -20,11 +37,62 @@ def get_summary(samples):
                             s.std(0, ddof=1)])
 
 
+def _summary_hip(samples, device, row_offset, chunk_cols):
+    import ctypes as C
+
+    from . import _lib
+
+    if not (isinstance(samples, (list, tuple)) and len(samples) and np.ndim(samples[0]) == 2):
+        a = np.asarray(samples)
+        samples = [a.reshape(-1, 1) if a.ndim == 1 else a]
+    blocks = []
+    for b in samples:
+        b = np.asarray(b)
+        if b.ndim != 2:
+            raise ValueError("get_summary: every block must be 2-D")
+        if b.dtype != np.float64 or not b.flags.c_contiguous:
+            b = np.ascontiguousarray(b, np.float64)
+        blocks.append(b)
+    n = blocks[0].shape[1]
+    if any(b.shape[1] != n for b in blocks):
+        raise ValueError("get_summary: the blocks' column counts differ")
+    rows = (C.c_longlong * len(blocks))(*[b.shape[0] for b in blocks])
+    ptrs = (C.c_void_p * len(blocks))(*[b.ctypes.data for b in blocks])
+    off = None
+    if row_offset is not None:
+        off = _lib.f64(np.asarray(row_offset).reshape(-1))
+        if off.size != sum(b.shape[0] for b in blocks):
+            raise ValueError("get_summary: row_offset needs one entry per row")
+    out = np.empty((5, max(n, 1)))  # n x 5 column-major
+    _lib.check(_lib.lib.nngp_summary(int(device), ptrs, rows, len(blocks), n, None if off is None else off.ctypes.data,
+                                     int(chunk_cols), out))
+    return np.ascontiguousarray(out.T)
+
+
+def summary_stats():
+    """HIP-event times and staging size of this thread's last device summary
+    (nngp_summary_stats)."""
+    import ctypes as C
+
+    from . import _lib
+
+    cp, kn, by, w = C.c_double(), C.c_double(), C.c_longlong(), C.c_int()
+    _lib.check(_lib.lib.nngp_summary_stats(C.byref(cp), C.byref(kn), C.byref(by), C.byref(w)))
+    return {"copy_ms": cp.value, "kernel_ms": kn.value, "staged_bytes": by.value, "chunk_cols": w.value}
+
+
 def _plogis(x):
     return 1 / (1 + np.exp(-x))
 
 
-def mcmc_nngp_estimate(mcmc_nngp_list, burn_in=0.5):
+def mcmc_nngp_estimate(mcmc_nngp_list, burn_in=0.5, field_backend="host", device=-1):
+    """estimate.R:9-96.  ``field_backend="hip"`` takes res["field"] (the one
+    summary as wide as the field) from the device get_summary on ``device``;
+    the covariance and fixed-effect summaries are a handful of columns and
+    stay on the host.  A burn_in that leaves no saved field row raises
+    NNGPError (status 1: no rows) there, where the host path returns NaNs."""
+    if field_backend not in ("host", "hip"):
+        raise ValueError(f"mcmc_nngp_estimate: field_backend must be 'host' or 'hip', not {field_backend!r}")
     L = mcmc_nngp_list
     recs = L["records"]
     first = next(iter(recs.values()))
@@ -90,6 +158,19 @@ def mcmc_nngp_estimate(mcmc_nngp_list, burn_in=0.5):
     fs = []
     saved = first["saved_field"]
     sel = saved > it * burn_in
+    if field_backend == "hip":
+        # saved_field increases, so the rows after burn-in are a suffix: each
+        # chain's block is a view of its records, the centring is the kernel's
+        # row offset (a mask that is no suffix falls back to a copy)
+        idx = np.nonzero(sel)[0]
+        suffix = idx.size > 0 and idx[0] + idx.size == sel.size
+        b0_rows = saved[sel].astype(int) - 1
+        for c in recs.values():
+            f = c["params"]["field"]
+            fs.append(f[idx[0]:] if suffix and f.shape[0] == sel.size else f[sel])
+        offs = np.concatenate([c["params"]["beta_0"][b0_rows, 0] for c in recs.values()])
+        res["field"] = get_summary(fs, backend="hip", device=device, row_offset=offs)
+        return res
     for c in recs.values():
         f = c["params"]["field"][sel]
         b0 = c["params"]["beta_0"][saved[sel].astype(int) - 1, 0]

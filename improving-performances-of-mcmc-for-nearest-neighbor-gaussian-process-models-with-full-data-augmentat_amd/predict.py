@@ -16,10 +16,14 @@ from .model import covparms
 
 
 def mcmc_nngp_predict_field(mcmc_nngp_list, predicted_locs, burn_in=0.5, n_cores=1, m=10, seed=1,
-                            device=-1, z_new=None):
+                            device=-1, z_new=None, summary_backend="host"):
     """predict.R:1-60.  ``z_new`` (optional) replaces the rnorm draws of the
     new locations (predict.R:50): z_new[k][i] = the normals of chain k's i-th
-    prediction; by default they come from numpy's generator seeded ``seed``."""
+    prediction; by default they come from numpy's generator seeded ``seed``.
+    ``summary_backend="hip"`` summarises the per-chain sample arrays on the
+    device (get_summary, no stacked copy); the samples are the same."""
+    if summary_backend not in ("host", "hip"):
+        raise ValueError(f"mcmc_nngp_predict_field: summary_backend must be 'host' or 'hip', not {summary_backend!r}")
     L = mcmc_nngp_list
     locs = L["locs"]
     predicted_locs = np.asarray(predicted_locs, np.float64)
@@ -54,9 +58,10 @@ def mcmc_nngp_predict_field(mcmc_nngp_list, predicted_locs, burn_in=0.5, n_cores
             samples[k] = sd * x[n:]
         out.append(samples)
     ctx.close()
-    allsamp = np.vstack(out)
+    summary = get_summary(out, backend="hip", device=device) if summary_backend == "hip" \
+        else get_summary(np.vstack(out))
     return {"predicted_locs": predicted_locs, "predicted_field_samples": out,
-            "predicted_field_summary": get_summary(allsamp)}
+            "predicted_field_summary": summary}
 
 
 def mcmc_nngp_predict_fixed_effects(mcmc_nngp_list, X_predicted, burn_in=0.5, n_cores=1,

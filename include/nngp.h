@@ -38,6 +38,8 @@
  *   nngp_sum_squared_residuals update_Gaussian.R:281
  *   nngp_record_field ........ records$field[i, ] = field, update_Gaussian.R:305-311
  *   nngp_records_stream ...... records$field in host memory while the chain runs (same lines)
+ *   nngp_summary ............. get_summary, Scripts/mcmc_nngp_estimate.R:1-6 (res$field,
+ *                              estimate.R:88-94; predicted_field_summary, predict.R:57-58)
  *   nngp_spmv / nngp_tri_solve sparse_chol %*% X (update_Gaussian.R:79,147) /
  *                              Matrix::solve (initialize.R:208, predict.R:46)
  */
@@ -51,7 +53,7 @@
 extern "C" {
 #endif
 
-#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues; 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
+#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
 #define NNGP_SHARD_ID_BYTES 128 /* RCCL unique id */
 #define NNGP_IPC_HANDLE_BYTES 192 /* HIP IPC handles of a tile shard's granule buffer, w replica, flags */
 
@@ -334,6 +336,40 @@ int nngp_shard_ipc_open(nngp_ctx* ctx, const unsigned char* handles, int len_eac
  * reader never performs a hidden collective.  A no-op on every other
  * context and on an up-to-date replica. */
 int nngp_shard_sync(nngp_ctx* ctx);
+
+/* ---------- posterior summaries (no context) ---------- */
+/* get_summary (Scripts/mcmc_nngp_estimate.R:1-6; its uses at estimate.R:88-94 and
+ * predict.R:57-58) of the row-wise stack of n_blocks host blocks; block k is
+ * block_rows[k] x n row-major with row pitch n.  row_offset (total rows, or NULL)
+ * is subtracted from each row.  out: n x 5 column-major (R matrix; columns mean,
+ * q0.025, median, q0.975, sd).  chunk_cols: 0 = automatic, else the number of
+ * columns staged per kernel launch.
+ * The quantiles are R's type 7 (numpy 'linear') on exactly selected order
+ * statistics, the mean is the sum in row order / rows, sd the two-pass one
+ * with divisor rows - 1 (NaN for one row); a column holding a NaN gives five
+ * NaNs.  A column's five numbers depend on that column alone: not on n, the
+ * chunking or the column's position.  At most 2^31 - 1 rows in total.
+ * The blocks are read where they lie (no stacked host copy): column chunks
+ * are staged into two device buffers, the copy of one chunk running beside
+ * the kernel of the chunk before.  Automatic chunk_cols keeps both buffers
+ * together within 1 GiB (never below 64 columns), and cuts a matrix that
+ * would fit one chunk into about four while a chunk keeps >= 65536 columns.
+ * The n x 5 result is held on the device as well and copied out once.
+ * device: HIP ordinal (-1: current); the calling thread's current device is
+ * the same after the call as before it.  NNGP_ERR_ARG: no rows, n < 1,
+ * n_blocks < 1, a null block. */
+int nngp_summary(int device, const double* const* blocks, const long long* block_rows,
+                 int n_blocks, long long n, const double* row_offset, int chunk_cols,
+                 double* out);
+/* Measurement: the calling thread's last successful summary -- HIP-event times
+ * of its staging copies and of its kernels (each summed over the chunks; they
+ * overlap, so the sum can exceed the call's wall time), the bytes staged and
+ * the chunk width used.  Any pointer may be NULL.  NNGP_ERR_STATE: none yet.
+ * A separate entry, like the sweep's timed form, so that the summary's own
+ * signature carries no measurement arguments: the times exist only inside the
+ * call (its streams and events are gone when it returns), and
+ * scripts/summary_time.py, the R wrapper and a C client all read them here. */
+int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols);
 
 /* ---------- measurement ---------- */
 /* nngp_sweep_chains bracketed by HIP events on the context's stream;

@@ -96,6 +96,15 @@ nngp_tri_solve <- function(ctx, which, u) .Call(C_nngp_tri_solve, ctx, as.intege
 nngp_tri_rescues <- function(ctx) .Call(C_nngp_tri_rescues, ctx)
 nngp_device_normals <- function(device, seed, sweep, n)
   .Call(C_nngp_device_normals, as.integer(device), as.double(seed), as.double(sweep), as.integer(n))
+# get_summary (Scripts/mcmc_nngp_estimate.R:1-6) of a samples x locations matrix on the device:
+# n x 5 with columns mean, q0.025, median, q0.975, sd (type-7 quantiles, as quantile()'s default)
+nngp_get_summary <- function(samples, device = -1L) {
+  if (!is.matrix(samples)) samples <- matrix(samples, ncol = 1)
+  storage.mode(samples) <- "double"
+  .Call(C_nngp_summary, as.integer(device), samples)
+}
+# HIP-event times (ms), staged bytes and chunk width of the last nngp_get_summary
+nngp_summary_stats <- function() .Call(C_nngp_summary_stats)
 # r = B (field - beta0) of the selected chain as the last sweep call left it (warm-call state)
 nngp_get_sweep_r <- function(ctx) .Call(C_nngp_get_sweep_r, ctx)
 

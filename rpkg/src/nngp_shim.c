@@ -442,6 +442,48 @@ SEXP C_nngp_device_normals(SEXP device, SEXP seed, SEXP sweep, SEXP n) {
   return z;
 }
 
+/* get_summary (estimate.R:1-6) of an S x n matrix of samples on the device:
+ * the column-major R matrix is brought to S row-major rows of n (the blocked
+ * transpose of nngp_rows.h, reading it as n row-major rows of S) and passed
+ * as one block; -> n x 5 with the reference's column names. */
+SEXP C_nngp_summary(SEXP device, SEXP samples) {
+  if (TYPEOF(samples) != REALSXP || !Rf_isMatrix(samples)) Rf_error("nngp: samples must be a numeric matrix");
+  const int S = Rf_nrows(samples), n = Rf_ncols(samples);
+  static const char* names[5] = {"mean", "q0.025", "median", "q0.975", "sd"};
+  SEXP rows = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)S * n));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n, 5));
+  nngp_rows_to_colmajor(REAL(samples), REAL(rows), n, n, S);
+  const double* block = REAL(rows);
+  const long long block_rows = S;
+  check(nngp_summary(as_int(device), &block, &block_rows, 1, n, NULL, 0, REAL(out)), NULL);
+  SEXP cn = PROTECT(Rf_allocVector(STRSXP, 5));
+  for (int i = 0; i < 5; ++i) SET_STRING_ELT(cn, i, Rf_mkChar(names[i]));
+  SEXP dn = PROTECT(Rf_allocVector(VECSXP, 2));
+  SET_VECTOR_ELT(dn, 1, cn);
+  Rf_setAttrib(out, Rf_install("dimnames"), dn);
+  UNPROTECT(4);
+  return out;
+}
+
+/* the last summary's HIP-event times (ms), staged bytes and chunk width */
+SEXP C_nngp_summary_stats(void) {
+  static const char* names[4] = {"copy_ms", "kernel_ms", "staged_bytes", "chunk_cols"};
+  double copy_ms = 0, kernel_ms = 0;
+  long long bytes = 0;
+  int cols = 0;
+  check(nngp_summary_stats(&copy_ms, &kernel_ms, &bytes, &cols), NULL);
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, 4));
+  SEXP nm = PROTECT(Rf_allocVector(STRSXP, 4));
+  REAL(out)[0] = copy_ms;
+  REAL(out)[1] = kernel_ms;
+  REAL(out)[2] = (double)bytes;
+  REAL(out)[3] = (double)cols;
+  for (int i = 0; i < 4; ++i) SET_STRING_ELT(nm, i, Rf_mkChar(names[i]));
+  Rf_setAttrib(out, R_NamesSymbol, nm);
+  UNPROTECT(2);
+  return out;
+}
+
 SEXP C_nngp_get_sweep_r(SEXP p) {
   nngp_ctx* c = get_ctx(p);
   SEXP r = PROTECT(Rf_allocVector(REALSXP, ctx_n(c)));
@@ -705,6 +747,8 @@ static const R_CallMethodDef call_methods[] = {
     E(C_nngp_tri_solve, 3),
     E(C_nngp_tri_rescues, 1),
     E(C_nngp_device_normals, 4),
+    E(C_nngp_summary, 2),
+    E(C_nngp_summary_stats, 0),
     E(C_nngp_get_sweep_r, 1),
     E(C_nngp_shard_unique_id, 0),
     E(C_nngp_shard_comm_init, 2),
