@@ -2,7 +2,10 @@
 // every nonzero B[k,i] appears exactly once, in its slot's stream range
 // (through ent_pos), in a chunk whose cells are sorted by row; padding is
 // inert and only at the stream tail.  Usage:
-//   layout_check <n> <m> <lanes_per_chain> <seed>   (prints "ok <stats>")
+//   layout_check <n> <m> <lanes_per_chain> <seed> [HUB]   (prints "ok <stats>")
+// HUB > 0: location 7 is given a column of B of HUB entries (hub_graph.h) --
+// one slot that fills most of a chunk, or, past lanes_per_chain * 16 entries,
+// a graph the planner must refuse ("FAIL build: <its message>", exit 1).
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -12,6 +15,7 @@
 #include <algorithm>
 
 #include "graph_prep.h"
+#include "hub_graph.h"
 
 using namespace nngp;
 
@@ -28,6 +32,7 @@ int main(int argc, char** argv) {
   const int m = argc > 2 ? std::atoi(argv[2]) : 10;
   const int LW = argc > 3 ? std::atoi(argv[3]) : 64;
   const int seed = argc > 4 ? std::atoi(argv[4]) : 1;
+  const int HUB = argc > 5 ? std::atoi(argv[5]) : 0;
   const int d = 2, b = m + 1;
   std::mt19937_64 g(seed);
   std::uniform_real_distribution<double> U(0, 1);
@@ -39,10 +44,15 @@ int main(int argc, char** argv) {
     for (int k = 0; k < d; ++k) locs[i + (size_t)k * n] = raw[ord[i] + (size_t)k * n];
   std::vector<int> nn, col;
   find_ordered_nn(locs.data(), n, d, m, nn);
-  const int K = greedy_coloring(nn.data(), n, b, col);
+  int K = greedy_coloring(nn.data(), n, b, col);
+  if (HUB > 0) REQUIRE(add_hub_column(nn, n, b, HUB, g, col, &K) == HUB);
   SweepLayout L;
   std::string err;
-  REQUIRE(build_sweep_layout(nn.data(), n, b, col.data(), locs.data(), d, LW, L, err));
+  if (!build_sweep_layout(nn.data(), n, b, col.data(), locs.data(), d, LW, L, err)) {
+    std::printf("FAIL build: %s\n", err.c_str());
+    return 1;
+  }
+  REQUIRE(HUB == 0 || L.max_collen == HUB);
   REQUIRE(L.K == K && L.LW == LW);
   // expected (row position, src) multiset per location
   std::vector<std::set<std::pair<int, int>>> want(n);

@@ -18,7 +18,11 @@
 // With WAVES > 0 (NT = 64): wave-local batches (one wave's each, rounds of
 // WAVES per colour, tiles.hip tile_phase_wl); the batches of a colour touch
 // disjoint rows, so emulating them one after another is the kernel's result.
-// Usage: tile_sweep_check <n> <m> <tiles> <chains> <seed> [NT RMAX G SPLIT SWEEPS WAVES]  (prints "ok <stats>")
+// With HUB > 0: location 7 is given a column of B of HUB entries (hub_graph.h):
+// one slot whose cells cover many threads (whole waves) of a batch and whose
+// draw nearly every other tile -- with G > 1 every other rank -- reads; past
+// NT * RMAX cells the planner must refuse ("FAIL build: <its message>").
+// Usage: tile_sweep_check <n> <m> <tiles> <chains> <seed> [NT RMAX G SPLIT SWEEPS WAVES HUB]  (prints "ok <stats>")
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -29,6 +33,7 @@
 #include <vector>
 
 #include "graph_prep.h"
+#include "hub_graph.h"
 
 using namespace nngp;
 
@@ -52,6 +57,7 @@ int main(int argc, char** argv) {
   const bool SPLIT = argc > 9 && std::atoi(argv[9]) != 0;
   const int sweeps = argc > 10 ? std::atoi(argv[10]) : 3;
   const int WAVES = argc > 11 ? std::atoi(argv[11]) : 0;  // wave-local batches (NT = 64) in rounds of WAVES
+  const int HUB = argc > 12 ? std::atoi(argv[12]) : 0;
   const int d = 2, b = m + 1;
   std::mt19937_64 g(seed);
   std::uniform_real_distribution<double> U(0, 1);
@@ -64,7 +70,8 @@ int main(int argc, char** argv) {
     for (int k = 0; k < d; ++k) locs[i + (size_t)k * n] = raw[ord[i] + (size_t)k * n];
   std::vector<int> nn, col;
   find_ordered_nn(locs.data(), n, d, m, nn);
-  const int K = greedy_coloring(nn.data(), n, b, col);
+  int K = greedy_coloring(nn.data(), n, b, col);
+  if (HUB > 0) REQUIRE(add_hub_column(nn, n, b, HUB, g, col, &K) == HUB);
   TileLayout L;
   std::string err;
   if (!build_tile_layout(nn.data(), n, b, col.data(), locs.data(), d, T, NT, RMAX, L, err, G, SPLIT, WAVES)) {
@@ -72,6 +79,7 @@ int main(int argc, char** argv) {
     return 1;
   }
   REQUIRE(L.K == K && L.T == std::min(T, n));
+  REQUIRE(HUB == 0 || L.max_collen == HUB);
   // per-chain B values (device layout: row rpos[k], position u), D, R, n_i, w, z
   std::vector<std::vector<double>> linv(C, std::vector<double>((size_t)n * b, 0.0));
   for (int ch = 0; ch < C; ++ch)
@@ -375,9 +383,30 @@ int main(int argc, char** argv) {
     lds[c] = tile_lds_bytes(L.max_rows, c, 512, K, L.max_batches, L.max_gslots);
     lds_rg[c] = tile_lds_bytes(0, c, 512, K, L.max_batches, L.max_gslots);
   }
+  // the longest column's slot: the threads of its batch it covers, the tiles
+  // that read its draw, the ranks of its remote-reader mask
+  int hub_threads = 0, hub_readers = 0, hub_ranks = 0;
+  {
+    int hx = 0;
+    std::vector<int> cl(n, 0);
+    for (size_t e = 0; e < (size_t)n * b; ++e)
+      if (nn[e] >= 0) ++cl[nn[e]];
+    for (int i = 0; i < n; ++i)
+      if (cl[i] > cl[L.compact_loc[hx]]) hx = slot_of[i];
+    for (const TileBatch& tb : L.batch)
+      if (hx >= tb.slot0 && hx < tb.slot0 + tb.nslots) {
+        const int f0 = L.slot_f0[hx] & 0xFFFFF, f1 = f0 + cl[L.compact_loc[hx]] - 1;
+        hub_threads = f1 / tb.R - f0 / tb.R + 1;
+      }
+    for (int t = 0; t < L.T; ++t)
+      for (int pc = t * K; pc < t * K + K; ++pc)
+        hub_readers += std::count(L.gslot.begin() + L.gslot_ptr[pc], L.gslot.begin() + L.gslot_ptr[pc + 1], hx) > 0;
+    if (G > 1) hub_ranks = __builtin_popcount(L.rmask[hx]);
+  }
   std::printf("ok K=%d T=%d G=%d max_rows=%d batches=%zu cells=%zu ghosts=%zu nb=%zu remote_puts=%lld maxrel=%.2e "
-              "layout=%016llx lds=%d,%d,%d,%d lds_rg=%d,%d,%d,%d cu_lds=%d\n", K, L.T, G, L.max_rows, L.batch.size(),
+              "layout=%016llx lds=%d,%d,%d,%d lds_rg=%d,%d,%d,%d cu_lds=%d max_collen=%d hub_threads=%d "
+              "hub_readers=%d hub_ranks=%d\n", K, L.T, G, L.max_rows, L.batch.size(),
               ncell, ng, L.nb.size(), remote_puts, maxrel, lh, lds[1], lds[2], lds[3], lds[4], lds_rg[1], lds_rg[2],
-              lds_rg[3], lds_rg[4], kTileCuLds);
+              lds_rg[3], lds_rg[4], kTileCuLds, L.max_collen, hub_threads, hub_readers, hub_ranks);
   return 0;
 }

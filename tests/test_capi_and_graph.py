@@ -249,6 +249,99 @@ def test_tile_sweep_emulation_wave_local_interior_first(tile_check_exe, n, m, ti
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
 
 
+@pytest.fixture(scope="module")
+def layout_check_exe(tmp_path_factory):
+    import subprocess
+
+    csrc = next(ROOT.glob("*_amd")) / "csrc"
+    exe = tmp_path_factory.mktemp("layout") / "layout_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", str(csrc), str(ROOT / "tests/cpp/layout_check.cpp"),
+                    str(csrc / "graph_prep.cpp"), "-o", str(exe)], check=True)
+    return exe
+
+
+def _kv(stdout):
+    return dict(x.split("=", 1) for x in stdout.split()[1:])
+
+
+# Irregular graphs (tests/cpp/hub_graph.h: one "hub" location whose column of B
+# has H entries, the rest of the graph uniform): the CPU side of
+# tests/test_gpu_irregular_graphs.py, same sizes -- the first place to look
+# when a device case there fails.
+@pytest.mark.parametrize("n,m,lw,H", [(3000, 5, 21, 300), (4000, 10, 32, 500), (6000, 5, 64, 1000)])
+def test_sweep_layout_invariants_hub_column(layout_check_exe, n, m, lw, H):
+    """The colour engine's layout with one slot that fills most of a chunk
+    (300 of 336, 500 of 512, 1000 of 1024 entries at 21, 32, 64 lanes per
+    chain): the invariants of test_sweep_layout_invariants."""
+    import subprocess
+
+    out = subprocess.run([str(layout_check_exe), str(n), str(m), str(lw), "1", str(H)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
+    assert int(_kv(out.stdout)["max_collen"]) == H
+
+
+@pytest.mark.parametrize("n,m,tiles,chains,nt,rmax,G,waves,H", [
+    (8000, 5, 24, 1, 512, 8, 1, 0, 3000),   # classic tiles: 3000 of 4096 cells
+    (8000, 5, 24, 1, 448, 8, 1, 0, 3000),   # exchange-wave tiles: 3000 of 3584 cells
+    (4000, 10, 24, 3, 64, 8, 1, 7, 500),    # wave-local batches: 500 of 512 cells, one slot per wave
+    (6000, 5, 24, 1, 256, 16, 8, 0, 1000),  # tile shard, G = 8: every other rank reads the hub's draw
+])
+def test_tile_sweep_emulation_hub_column(tile_check_exe, n, m, tiles, chains, nt, rmax, G, waves, H):
+    """The tile sweep's emulation (test_tile_sweep_emulation, 1e-11 against
+    the serial sweep) with a hub slot: its cells cover at least H / RMAX
+    threads of its batch (whole waves, so most waves of the batch hold no
+    segment start), its draw is a foreign slot of every other tile, and in a
+    tile shard its remote-reader mask has every other rank set."""
+    import subprocess
+
+    out = subprocess.run([str(tile_check_exe), str(n), str(m), str(tiles), str(chains), "1", str(nt), str(rmax),
+                          str(G), "0", "2", str(waves), str(H)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
+    kv = _kv(out.stdout)
+    assert int(kv["max_collen"]) == H and int(kv["T"]) == tiles
+    assert int(kv["hub_threads"]) >= -(-H // rmax) and int(kv["hub_threads"]) <= nt
+    assert int(kv["hub_readers"]) == tiles - 1
+    assert int(kv["hub_ranks"]) == (G - 1 if G > 1 else 0)
+
+
+@pytest.mark.parametrize("n,m,lw", [(3000, 5, 16), (3000, 5, 21), (4000, 10, 32), (6000, 5, 64)])
+def test_sweep_layout_refuses_column_longer_than_a_chunk(layout_check_exe, n, m, lw):
+    """build_sweep_layout at H = lanes x 16 + 1: returns false with its
+    message (the column length, the cap, the advice) -- no crash, no layout;
+    at H = lanes x 16 the layout is built and keeps its invariants."""
+    import subprocess
+
+    cap = lw * 16
+    out = subprocess.run([str(layout_check_exe), str(n), str(m), str(lw), "1", str(cap + 1)], capture_output=True,
+                         text=True)
+    assert out.returncode == 1, (out.returncode, out.stdout + out.stderr)
+    assert out.stdout.startswith(f"FAIL build: a column of B has {cap + 1} entries, more than a sweep chunk ({cap}; "
+                                 "use fewer chains per context)"), out.stdout
+    # the cap itself is a legal column: one slot fills the whole chunk
+    out = subprocess.run([str(layout_check_exe), str(n), str(m), str(lw), "1", str(cap)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
+    assert int(_kv(out.stdout)["max_collen"]) == cap
+
+
+@pytest.mark.parametrize("n,m,chains,nt,rmax,waves", [(8000, 5, 1, 512, 8, 0), (8000, 5, 1, 448, 8, 0),
+                                                      (4000, 10, 3, 64, 8, 7), (6000, 5, 2, 256, 8, 0)])
+def test_tile_layout_refuses_column_longer_than_a_batch(tile_check_exe, n, m, chains, nt, rmax, waves):
+    """build_tile_layout at H = NT x RMAX + 1 (4097 classic, 3585
+    exchange-wave, 513 wave-local, 2049 chain-split cells): returns false
+    with its message; at H = NT x RMAX the layout is built and the emulation
+    passes (the cap itself is a legal column)."""
+    import subprocess
+
+    cap = nt * rmax
+    args = [str(tile_check_exe), str(n), str(m), "24", str(chains), "1", str(nt), str(rmax), "1", "0", "1", str(waves)]
+    out = subprocess.run(args + [str(cap + 1)], capture_output=True, text=True)
+    assert out.returncode == 1, (out.returncode, out.stdout + out.stderr)
+    assert out.stdout.startswith("FAIL build: tile layout: a column of B is longer than a batch"), out.stdout
+    out = subprocess.run(args + [str(cap)], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
+    assert int(_kv(out.stdout)["max_collen"]) == cap and int(_kv(out.stdout)["hub_threads"]) == nt
+
+
 def test_interior_first_wave_local_barrier_counts_match():
     """Interior-first wave-local tiles (tiles.hip tile_phase_wlib, opt-in): the
     cell waves pass three workgroup barriers per phase (A: the hand-off is in,
