@@ -198,13 +198,11 @@ struct nngp_ctx {
   double* dwx_d = nullptr;        // n x C granules of 16 B
   bool rglobal = false;           // tiles keep r in global memory (rg_d) instead of LDS
   bool warm_on = false;           // warm sweep calls allowed (tile engine, not a shard; NNGP_SWEEP_WARM=0: off)
-  bool tcs = false;               // chain-split tile launches (one chain per workgroup, kernels.hip sweep_tiles_cs_kernel)
   int txw = 0;                    // exchange-wave tiles (tiles.hip tile_phase_xw): layout cut for NT - 64 cell threads
   int cus = 0;                    // compute units of the device
   int tresident = 0;              // tile workgroups resident per CU (occupancy query of the instantiation)
   int engine_fallback = 0;        // 0: none, 1: tile layout unsuitable (LDS, shape), 2: residency, 3: forced colours
   std::string engine_note;        // why this sweep engine (nngp_ctx_engine_note)
-  int tstagger = 0;               // chain-split: start offset per chain (NNGP_TILE_STAGGER, 100 MHz ticks)
   int tvariant = 0;               // NNGP_TILE_VARIANT (probe builds): experiment bits
   int tile_rows_needed = 0;       // largest local rows of a tile of the layout built here (nngp_info)
   int lds_max = 0;                // LDS bytes per CU of the device
@@ -734,17 +732,20 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
       T = std::max(G, T / G * G);  // a multiple of the ranks
       std::string terr;
       int NT = kTileNT;
-      // NNGP_TILE_CHAINS=split (2-4 chains, one GPU): one workgroup per
-      // (chain, tile), 256-thread tiles, the chains' workgroups of a tile
-      // interleaved on its CU (kernels.hip sweep_tiles_cs_kernel)
+      // a tile's workgroup runs every chain of the context ("joint").  The
+      // chain-split launches (NNGP_TILE_CHAINS=split) were measured slower and
+      // removed: asking for them is an error, not a silent
+      // default
       const char* tch = std::getenv("NNGP_TILE_CHAINS");
       const std::string tcs = tch ? tch : "";
-      if (tcs != "" && tcs != "split" && tcs != "joint") {
+      if (tcs == "split") {
         delete c;
-        return fail_msg(nullptr, NNGP_ERR_ARG, "NNGP_TILE_CHAINS must be split or joint");
+        return fail_msg(nullptr, NNGP_ERR_ARG, "NNGP_TILE_CHAINS=split: the chain-split tile launches were removed");
       }
-      const bool csplit = tcs == "split" && shard_G == 0 && n_chains >= 2;
-      if (csplit) NT = 256;
+      if (tcs != "" && tcs != "joint") {
+        delete c;
+        return fail_msg(nullptr, NNGP_ERR_ARG, "NNGP_TILE_CHAINS: only joint is supported");
+      }
       if (const char* te = std::getenv("NNGP_TILE_NT")) NT = std::atoi(te);
       if (NT != 256 && NT != 512 && NT != 1024) {
         delete c;
@@ -755,7 +756,7 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
       // launch at the headline (two batches per colour, and the next colour's
       // stream no longer overlaps the hand-off with one register set)
       const char* tsp = std::getenv("NNGP_TILE_SPLIT");
-      const bool split = !csplit && tile_double_buffer(n_chains, NT) == 0 && tsp && std::string(tsp) == "1";
+      const bool split = tile_double_buffer(n_chains, NT) == 0 && tsp && std::string(tsp) == "1";
       // a tile's own rows alone beyond the LDS: no layout to build (n = 8e6 on
       // one GPU would spend ~30 s building one that cannot run)
       // The colour engine refuses a column of B longer than its sweep chunk
@@ -769,9 +770,8 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
       const bool hopeless = !rg_forced && rows_beyond_lds;
       if (hopeless) terr = "tile layout: a tile's own rows exceed the LDS";
       // cells per own batch: NT x RMAX of the kernel; NNGP_TILE_BATCH_CELLS
-      // may lower it (e.g. joint tiles cut like chain-split ones, for bitwise
-      // comparisons)
-      int rmax_l = csplit ? tile_rmax_cs(NT) : tile_rmax(n_chains, NT);
+      // may lower it
+      int rmax_l = tile_rmax(n_chains, NT);
       // exchange-wave tiles (default for 512-thread LDS tiles; NNGP_TILE_XW=0
       // turns them off): the last wave of the workgroup polls the hand-offs,
       // the batches are cut for the other NT - 64 threads.  Measured at the
@@ -793,7 +793,7 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
       const bool wl_env = twl ? std::string(twl) == "1" : (n_chains >= 3 && !rg_forced);
       // interior-first layouts run on wave-local batches (tiles.hip
       // tile_phase_wlib) or, without the exchange wave, on workgroup batches
-      const bool xw = !csplit && (!split || wl_env) && (!rg_forced || wl_env) && NT == 512 && xwm == 1;
+      const bool xw = (!split || wl_env) && (!rg_forced || wl_env) && NT == 512 && xwm == 1;
       const bool wl = xw && wl_env;
       const int NTL = wl ? 64 : (xw ? NT - 64 : NT);  // the layout's cell threads of a batch
       if (const char* bc = std::getenv("NNGP_TILE_BATCH_CELLS"))
@@ -803,19 +803,7 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
                                   split, wl ? NT / 64 - 1 : 0);
       c->tl.NTK = NT;
       c->txw = xw ? (wl ? 2 : 1) : 0;
-      if (ok && csplit) {
-        // n_chains workgroups of one chain per CU
-        const int need1 = tile_lds_bytes(c->tl.max_rows, 1, NT, c->tl.K, c->tl.max_batches, c->tl.max_gslots);
-        if (NT != 256 || (long long)need1 * n_chains > lds_max) {
-          ok = false;
-          terr = "chain-split tiles need 256 threads and " + std::to_string(need1) + " B of LDS per chain x " +
-                 std::to_string(n_chains) + " chains per CU (device: " + std::to_string(lds_max) + ")";
-        } else {
-          c->tcs = true;
-          if (const char* sg = std::getenv("NNGP_TILE_STAGGER")) c->tstagger = std::max(0, std::atoi(sg));
-        }
-      }
-      const int need = ok && !csplit ? tile_lds_bytes(c->tl.max_rows, n_chains, NT, c->tl.K, c->tl.max_batches, c->tl.max_gslots) : 0;
+      const int need = ok ? tile_lds_bytes(c->tl.max_rows, n_chains, NT, c->tl.K, c->tl.max_batches, c->tl.max_gslots) : 0;
       // NNGP_TILE_R=global: the tiles' r in global memory (tiles.hip RG; one
       // GPU, or a tile shard with 512-thread tiles),
       // one GPU, for layouts beyond the LDS.  Opt-in: at n = 1e7, m = 20 (one
@@ -831,7 +819,7 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
       // test_configs4_tile_shard_geometry): the layout is rebuilt
       // for the RG kernel's 512 cell threads
       // One GPU takes the same route when the colour engine cannot either
-      if (ok && (shard_G > 1 || colours_refuse) && !force_rg && need > lds_max && NT == 512 && !csplit && !split) {
+      if (ok && (shard_G > 1 || colours_refuse) && !force_rg && need > lds_max && NT == 512 && !split) {
         ok = build_tile_layout(nn.data(), n, b, coloring, locs, d, T, NT, tile_rmax(n_chains, NT), c->tl, terr, G,
                                false, 0);
         c->tl.NTK = NT;
@@ -853,8 +841,7 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
       // residency: the persistent launch needs all its workgroups on the device
       // at once (tiles poll each other's granules); the occupancy of exactly
       // the instantiation that will run, at its LDS, times the CUs must cover
-      // the launch's grid (one rank's tiles per process; every chain's tiles
-      // of a chain-split launch)
+      // the launch's grid (one rank's tiles per process)
       if (ok) {
         TileDev Dq;
         Dq.C = n_chains;
@@ -869,18 +856,11 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
           }
         TileShard shq;
         int per_cu = 0;
-        hipError_t oe;
-        if (csplit) {
-          // by construction: the kernel's register budget is pinned to C
-          // workgroups per CU (amdgpu_waves_per_eu) and its LDS floor allows
-          // no more than C (the occupancy query rejects this kernel)
-          oe = hipSuccess;
-          per_cu = n_chains;
-        } else
-          oe = launch_sweep_tiles(nullptr, Dq, TileLaunch(), c->tl.max_rows, NT, c->tl.max_batches, c->tl.max_gslots,
-                                  shard_G > 0 ? &shq : nullptr, 0, &per_cu);
+        const hipError_t oe =
+            launch_sweep_tiles(nullptr, Dq, TileLaunch(), c->tl.max_rows, NT, c->tl.max_batches, c->tl.max_gslots,
+                               shard_G > 0 ? &shq : nullptr, 0, &per_cu);
         (void)hipGetLastError();
-        const long long grid = csplit ? (long long)T * n_chains : (long long)(T / G);
+        const long long grid = T / G;
         c->tresident = oe == hipSuccess ? per_cu : 0;
         if (oe != hipSuccess || (long long)per_cu * cus < grid) {
           ok = false;
@@ -908,8 +888,7 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
         c->engine_note = "tiles: " + std::to_string(T) + " tiles of " + std::to_string(NT) + " threads, " +
                          std::to_string(c->tresident) + " resident per CU x " + std::to_string(cus) + " CUs" +
                          (c->rglobal ? ", r in global memory" : "") + (c->txw == 2 ? ", exchange wave, wave-local batches" : c->txw ? ", exchange wave" : "") +
-                         (c->tl.split ? ", interior first" : "") +
-                         (c->tcs ? ", chain-split" : "");
+                         (c->tl.split ? ", interior first" : "");
         if (shard_G > 0) {
           c->shard = true;
           c->tG = G;
@@ -920,7 +899,6 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
         c->tile_rows_needed = c->tl.max_rows;
         c->tl = TileLayout();
         c->txw = 0;
-        c->tcs = false;
         c->rglobal = false;
         if (c->engine_fallback == 0) c->engine_fallback = 1;
         c->engine_note = "colours (tile engine not used: " + terr + ")";
@@ -1329,7 +1307,7 @@ int nngp_ctx_info(const nngp_ctx* c, nngp_info* info) {
   info->tile_ghost_pass = c->engine == 1 ? c->tl.NTK * tile_gmax(c->tl.NTK) : 0;
   info->tile_ghost_cells_max = 0;
   info->tile_r_global = c->rglobal ? 1 : 0;
-  info->tile_chain_split = c->tcs ? 1 : 0;
+  info->tile_chain_split = 0;  // (ABI: the chain-split launches were removed)
   info->tile_resident_per_cu = c->engine == 1 ? c->tresident : 0;
   info->engine_fallback = c->engine_fallback;
   info->tile_exchange_wave = c->txw ? 1 : 0;
@@ -1956,14 +1934,8 @@ static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double*
       a.slot_dpos = c->slot_dpos_d;
       a.field = fp;
     }
-    if (c->tcs) {
-      a.stagger = c->tstagger;
-      HIPCHK(c, launch_sweep_tiles_cs(c->st, tile_dev(c), a, c->tl.max_rows, c->tl.NTK, c->tl.max_batches,
-                                      c->tl.max_gslots));
-    } else {
-      HIPCHK(c, launch_sweep_tiles(c->st, tile_dev(c), a, c->tl.max_rows, c->tl.NTK, c->tl.max_batches,
-                                    c->tl.max_gslots));
-    }
+    HIPCHK(c, launch_sweep_tiles(c->st, tile_dev(c), a, c->tl.max_rows, c->tl.NTK, c->tl.max_batches,
+                                  c->tl.max_gslots));
     HIPCHK(c, hipMemcpyAsync(c->tmo_h, c->ctl_d + 2, sizeof(unsigned), hipMemcpyDeviceToHost, c->st));
   }
   if ((parts & kColours) && c->engine == 0) {

@@ -176,21 +176,12 @@ struct TileBatchRegs {
 };
 
 // index of item u (= slot-in-batch q x C + chain) of the batch at slot x0 in
-// the per-slot x chain arrays (dr, w_slot, granules).  CS = their chain
-// stride: C, or (chain-split launches: one chain per workgroup, C = 1) the
-// context's chain count, the chain's offset folded into the pointers
-template <int C, int CS>
-__device__ __forceinline__ size_t tile_xu(int x0, int u) {
-  if constexpr (CS == C) {
-    return (size_t)x0 * C + u;
-  } else {
-    const int q = u / C;
-    return (size_t)(x0 + q) * CS + (u - q * C);
-  }
-}
+// the per-slot x chain arrays (dr, w_slot, granules): chain stride C
+template <int C>
+__device__ __forceinline__ size_t tile_xu(int x0, int u) { return (size_t)x0 * C + u; }
 
 // the batch's per-slot records (the draw preparation waits for them)
-template <int C, int NT, int RMAX, int SH, int CS = C>
+template <int C, int NT, int RMAX, int SH>
 __device__ __forceinline__ void tile_load_items(const TileDev& D, const int4 B, TileBatchRegs<C, NT, RMAX>& b, int t) {
   b.ns = B.z; b.x0 = B.w;
 #pragma unroll
@@ -198,7 +189,7 @@ __device__ __forceinline__ void tile_load_items(const TileDev& D, const int4 B, 
     const int u = t + k * NT;
     if (u < b.ns * C) {
       const int q = u / C;
-      const size_t xu = tile_xu<C, CS>(b.x0, u);  // = (x0 + q) * CS + chain
+      const size_t xu = tile_xu<C>(b.x0, u);  // = (x0 + q) * C + chain
       const int2 si = D.sinfo[b.x0 + q];
       b.nobs[k] = si.x;
       b.flag[k] = si.y;
@@ -236,16 +227,16 @@ __device__ __forceinline__ void tile_load_cells(const TileDev& D, const int4 B, 
   }
 }
 
-template <int C, int NT, int RMAX, int SH, int CS = C>
+template <int C, int NT, int RMAX, int SH>
 __device__ __forceinline__ void tile_load_batch(const TileDev& D, const int4 B, TileBatchRegs<C, NT, RMAX>& b, int t) {
-  tile_load_items<C, NT, RMAX, SH, CS>(D, B, b, t);
+  tile_load_items<C, NT, RMAX, SH>(D, B, b, t);
   tile_load_cells<C, NT, RMAX>(D, B, b, t);
 }
 
 // everything of the Gibbs draw but acc: P = D/s2 + n/t2, w' = (cR - acc/s2)/P
 // + z/sqrt(P) with cR = R/t2 + D w/s2 (w of an own slot is constant until its
 // colour, so this runs a colour ahead, during the previous hand-off)
-template <int C, int NT, int RMAX, int CS = C>
+template <int C, int NT, int RMAX>
 __device__ __forceinline__ void tile_prep_items(const TileDev& D, const TileLaunch& a, const double* sc_s,
                                                 const unsigned long long* seed_s, int s,
                                                 TileBatchRegs<C, NT, RMAX>& b, int t, int var = 0) {
@@ -259,7 +250,7 @@ __device__ __forceinline__ void tile_prep_items(const TileDev& D, const TileLaun
       // var (NNGP_TILE_VARIANT, probe timing experiments only, wrong results):
       // 2 = no normals, 4 = no records
       if (var & 2) z = 0.0;
-      else if (a.z_in) z = a.z_in[((size_t)s * D.n + b.x0 + q) * CS + ch];
+      else if (a.z_in) z = a.z_in[((size_t)s * D.n + b.x0 + q) * C + ch];
       else z = normal_loc(seed_s[2 * ch], seed_s[2 * ch + 1] + s, (uint32_t)b.loc[k]);
       const double a0 = (var & 4) ? 1.0 : b.a0[k], a1 = (var & 4) ? 0.5 : b.a1[k], wk = (var & 4) ? 0.0 : b.w[k];
       const double P = a0 * inv_s2 + (double)((var & 4) ? 1 : b.nobs[k]) * inv_t2;
@@ -479,7 +470,7 @@ __device__ __forceinline__ void tile_products(const TB& b, int R, const double* 
   }
 }
 
-template <int C, int NT, int RMAX, int PROBE, int SH, int CS = C>
+template <int C, int NT, int RMAX, int PROBE, int SH>
 __device__ __forceinline__ void tile_own_draw(const TileDev& D, const TileLaunch& a, const TileShard& sh, TileState& S,
                                               TileBatchRegs<C, NT, RMAX>& b, unsigned epoch) {
   constexpr int IMAX = TileBatchRegs<C, NT, RMAX>::IMAX;
@@ -565,7 +556,7 @@ __device__ __forceinline__ void tile_own_draw(const TileDev& D, const TileLaunch
     if (u < nit) {
       const int ch = u % C;
       double dw = 0.0;
-      const size_t xu = tile_xu<C, CS>(b.x0, u);
+      const size_t xu = tile_xu<C>(b.x0, u);
       if ((a.chain_mask >> ch) & 1) {
         const double wn = (b.a0[k] - S.sc_s[2 * ch] * acc_s[u]) * b.a1[k] + b.zs[k];
         dw = wn - b.w[k];
@@ -659,7 +650,7 @@ __device__ __forceinline__ void tile_cells_landed(const TileBatchRegs<C, NT, RMA
 // the normals pregenerated by a separate kernel -- no Philox here,
 // 132 instead of 255 VGPRs at 1 chain --, double buffering at 3 chains, an L2
 // prefetch of the next stream during the own work, other load orders.)
-template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int CS = C>
+template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH>
 __device__ __forceinline__ void tile_phase(const TileDev& D, const TileLaunch& a, const TileShard& sh, TileState& S, int ph,
                                            TileBatchRegs<C, NT, RMAX>& cur, TileBatchRegs<C, NT, RMAX>& nxt,
                                            TileGhostRegs<C, GMAX>& gr, TileGhostRegs<C, GMAX>& grn) {
@@ -685,7 +676,7 @@ __device__ __forceinline__ void tile_phase(const TileDev& D, const TileLaunch& a
   if (DB) {
     // the next colour's first batch (and ghost chunk): their HBM stream
     // overlaps this colour's work (two register sets)
-    if (more) tile_load_batch<C, NT, RMAX, SH, CS>(D, S.batch_s[S.bptr_s[cn]], nxt, t);
+    if (more) tile_load_batch<C, NT, RMAX, SH>(D, S.batch_s[S.bptr_s[cn]], nxt, t);
     if (has_next && gn1 > gn0) tile_load_ghosts<C, NT, GMAX>(D, gn0, gn1, grn, t);
   }
   // ---- 1. own batches.  One register set (!DB): after the draw of the last
@@ -698,15 +689,15 @@ __device__ __forceinline__ void tile_phase(const TileDev& D, const TileLaunch& a
   for (int bi = bfirst; bi < bend; ++bi) {
     if (bi != bfirst) {  // rare: a colour with more than one batch in this tile
       __syncthreads();   // acc_s is indexed by slot-in-batch: every wave is done with the last batch
-      tile_load_batch<C, NT, RMAX, SH, CS>(D, S.batch_s[bi], cur, t);
-      tile_prep_items<C, NT, RMAX, CS>(D, a, S.sc_s, S.seed_s, s, cur, t);
+      tile_load_batch<C, NT, RMAX, SH>(D, S.batch_s[bi], cur, t);
+      tile_prep_items<C, NT, RMAX>(D, a, S.sc_s, S.seed_s, s, cur, t);
     }
-    tile_own_draw<C, NT, RMAX, PROBE, SH, CS>(D, a, sh, S, cur, epoch);
+    tile_own_draw<C, NT, RMAX, PROBE, SH>(D, a, sh, S, cur, epoch);
     const int R = cur.R;
     if (!DB && bi + 1 == bend) {
-      if (more) tile_load_items<C, NT, RMAX, SH, CS>(D, S.batch_s[S.bptr_s[cn]], nxt, t);
+      if (more) tile_load_items<C, NT, RMAX, SH>(D, S.batch_s[S.bptr_s[cn]], nxt, t);
       if (g1 > g0) tile_load_ghosts<C, NT, GMAX>(D, g0, g1, gr, t);
-      if (pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * CS + t % C) * 16), 0, SH ? kGranAuxSys : kGranAux);
+      if (pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * C + t % C) * 16), 0, SH ? kGranAuxSys : kGranAux);
     }
     tile_own_scatter<C, NT, RMAX, PROBE>(S, cur, R);
   }
@@ -715,19 +706,19 @@ __device__ __forceinline__ void tile_phase(const TileDev& D, const TileLaunch& a
   // draw scalars, then (two register sets) the first poll
   if (!DB) {
     if (bend == bfirst) {  // no own batch of this colour in the tile
-      if (more) tile_load_items<C, NT, RMAX, SH, CS>(D, S.batch_s[S.bptr_s[cn]], nxt, t);
+      if (more) tile_load_items<C, NT, RMAX, SH>(D, S.batch_s[S.bptr_s[cn]], nxt, t);
       if (g1 > g0) tile_load_ghosts<C, NT, GMAX>(D, g0, g1, gr, t);
-      if (pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * CS + t % C) * 16), 0, SH ? kGranAuxSys : kGranAux);
+      if (pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * C + t % C) * 16), 0, SH ? kGranAuxSys : kGranAux);
     }
     // the next batch's draw scalars before its cells go out: the cells' loads
     // are conditional (rows past R), so a wait for the records issued before
     // them would also wait for every cell
-    if (more) tile_prep_items<C, NT, RMAX, CS>(D, a, S.sc_s, S.seed_s, sn, nxt, t);
+    if (more) tile_prep_items<C, NT, RMAX>(D, a, S.sc_s, S.seed_s, sn, nxt, t);
     if (more) tile_load_cells<C, NT, RMAX>(D, S.batch_s[S.bptr_s[cn]], nxt, t);
   } else if (more) {
-    tile_prep_items<C, NT, RMAX, CS>(D, a, S.sc_s, S.seed_s, sn, nxt, t);
+    tile_prep_items<C, NT, RMAX>(D, a, S.sc_s, S.seed_s, sn, nxt, t);
   }
-  if (DB && pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * CS + t % C) * 16), 0, SH ? kGranAuxSys : kGranAux);
+  if (DB && pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * C + t % C) * 16), 0, SH ? kGranAuxSys : kGranAux);
   TSTAMP(S, 5);
   TLSTAMP(S, 4);
   if (!DB) {  // the next phase's first foreign slot indices (complete once the polls below have waited)
@@ -743,7 +734,7 @@ __device__ __forceinline__ void tile_phase(const TileDev& D, const TileLaunch& a
     if (u < nfi) {
       const int x = u0 == 0 ? gsl_pref : D.gslot[gs0 + u / C];
       const int ch = u % C;
-      const int off = (int)(((size_t)x * CS + ch) * 16);
+      const int off = (int)(((size_t)x * C + ch) * 16);
       u32x4_t g = u0 == 0 ? gfirst : __builtin_amdgcn_raw_buffer_load_b128(S.gran, off, 0, SH ? kGranAuxSys : kGranAux);
       double dw = 0.0;
       for (unsigned spins = 0;; ++spins) {
@@ -969,7 +960,7 @@ __device__ __forceinline__ void tile_own_wl(const TileDev& D, const TileLaunch& 
     if (u < nit) {
       const int ch = u % C;
       double dw = 0.0;
-      const size_t xu = tile_xu<C, C>(b.x0, u);
+      const size_t xu = tile_xu<C>(b.x0, u);
       if ((a.chain_mask >> ch) & 1) {
         const double wn = (b.a0[k] - S.sc_s[2 * ch] * acc_s[u]) * b.a1[k] + b.zs[k];
         dw = wn - b.w[k];
@@ -1344,20 +1335,31 @@ __device__ __forceinline__ void tile_phase_cells(const TileDev& D, const TileLau
 // LDS (n = 1e7 on one GPU).  A row takes at most one update per colour (one
 // member per colour), so the scatter and the ghost adds stay plain
 // read-modify-writes; the phase barriers order them for the workgroup.
-// CS: chain stride of the per-slot arrays.  CS == C: the workgroup runs every
-// chain of the context (one workgroup per tile).  CS > C = 1 (chain-split,
-// sweep_tiles_cs_kernel): workgroup b runs chain b / T of tile b % T -- the
-// chains are independent Markov chains, so the CS workgroups of a tile share
-// its CU and each one's stream and hand-off waits overlap the others' work.
-// Chain-major numbering: the dispatcher places chain 0's tiles first, so a
-// chain never waits on a tile of its own that is not resident.
+//
+// One workgroup per tile runs every chain of the context (C).  The schedule
+// of the phase loop is picked by XW and IB:
+//  XW = 0, classic tiles: every wave holds cells and polls the hand-off
+//    itself (tile_phase; DB: two batch register sets, phases alternate them;
+//    IB: tile_phase_ib on a split layout);
+//  XW = 1, exchange-wave tiles: the last wave runs tile_phase_xw, the other
+//    NT - 64 threads tile_phase_cells on workgroup batches (r in LDS only);
+//  XW = 2, wave-local batches: the last wave runs tile_phase_xw, every other
+//    wave tile_phase_wl (IB: tile_phase_wlib, the exchange wave one phase
+//    behind) on batches of its own (r in LDS or, RG, global).
+// SH: a tile shard's launch (the tile's rank picks its TileDev, draws go to
+// the reader ranks' granule buffers too).  PROBE: 1 segment sums, 2 timeline.
+// Around the loop: the prologue brings r of the local rows and the tile's
+// metadata into LDS (a warm call's beta_0 shift applied on the way), the
+// epilogue writes the field of the tile's own slots and r back.
+// (A launch with one chain per workgroup, "chain-split", was measured slower
+// and removed: DESIGN.md §0, §3.)
 constexpr int kTailU = 4;  // slots / rows per thread and pass of the closing write-backs
-template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int RG, int IB, int CS, int XW = 0>
+template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int RG, int IB, int XW = 0>
 __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a, const TileShard& sh) {
-  static_assert(!XW || ((!RG || XW == 2) && (!IB || XW == 2) && CS == C),
-                "exchange-wave tiles: joint chains; split layouts and r in global memory only with wave-local batches");
+  static_assert(!XW || ((!RG || XW == 2) && (!IB || XW == 2)),
+                "exchange-wave tiles: split layouts and r in global memory only with wave-local batches");
   constexpr int NTC = XW ? NT - 64 : NT;  // cell threads
-  constexpr int CM = CS == C ? tile_r_chain_major(C, RG, SH, XW) : 0;  // r_s layout (tile_r_index)
+  constexpr int CM = tile_r_chain_major(C, RG, SH, XW);  // r_s layout (tile_r_index)
   using BR = TileBatchRegs<C, NTC, RMAX>;
   constexpr int NW = NT / 64;
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -1365,22 +1367,6 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
   int Tg = SH ? sh.tile0 + (int)blockIdx.x : (int)blockIdx.x;
   const int rk = SH ? Tg / sh.Tl : 0;
   TileDev D = SH ? sh.devs[rk - sh.rank0] : D0;
-  int ch0 = 0;
-  if constexpr (CS != C) {
-    static_assert(C == 1 && !SH && !RG && !IB && !PROBE, "chain-split: one chain per workgroup, single GPU");
-    ch0 = Tg / D.T;
-    Tg -= ch0 * D.T;
-    D.cell_val += (size_t)ch0 * D.n_cells;
-    D.gval += (size_t)ch0 * D.n_gcells;
-    D.dr += ch0;
-    D.w_slot += ch0;
-    D.dwx += 2 * ch0;  // 16-B granules
-    D.r += ch0;
-    D.scal += ch0;
-    D.b1 += ch0;
-    a.chain_mask >>= ch0;
-    if (a.z_in) a.z_in += ch0;
-  }
   TileState S;
   S.G = SH ? sh.G : 1;
   S.T = Tg; S.t = threadIdx.x; S.lane = S.t & 63; S.wv = S.t >> 6; S.K = D.K;
@@ -1419,7 +1405,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
   for (int ch = 0; ch < C; ++ch) dsh[ch] = D.scal[ch].dshift;
   for (int lr = t; lr < nrows; lr += NT) {
     const int row = D.erow[row0 + lr];
-    const size_t g = (size_t)row * CS;
+    const size_t g = (size_t)row * C;
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {
       const double v = D.r[g + ch];
@@ -1454,7 +1440,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
     // is tile-major, the batches cover it in order) moved by -d before any
     // batch loads it; the stores are this workgroup's, ordered by the barrier
     const int x0 = S.batch_s[0].w, x1 = S.batch_s[nbt - 1].w + S.batch_s[nbt - 1].z;
-    for (int u = t; u < (x1 - x0) * C; u += NT) D.w_slot[tile_xu<C, CS>(x0, u)] -= S.dsh_s[u % C];
+    for (int u = t; u < (x1 - x0) * C; u += NT) D.w_slot[tile_xu<C>(x0, u)] -= S.dsh_s[u % C];
     __syncthreads();
   }
   if constexpr (XW) {
@@ -1528,28 +1514,22 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
   BR A, B;  // batch register sets: the current colour's and (DB) the next one's
   TileGhostRegs<C, GMAX> GA, GB;
   if (S.nph > 0 && S.bptr_s[0] < S.bptr_s[1]) {
-    tile_load_batch<C, NT, RMAX, SH, CS>(D, S.batch_s[S.bptr_s[0]], A, t);
-    tile_prep_items<C, NT, RMAX, CS>(D, a, S.sc_s, S.seed_s, 0, A, t);
+    tile_load_batch<C, NT, RMAX, SH>(D, S.batch_s[S.bptr_s[0]], A, t);
+    tile_prep_items<C, NT, RMAX>(D, a, S.sc_s, S.seed_s, 0, A, t);
   }
   if (DB && S.nph > 0 && S.gptr_s[0] < S.gptr_s[1]) tile_load_ghosts<C, NT, GMAX>(D, S.gptr_s[0], S.gptr_s[1], GA, t);
   if (S.nph > 0 && t < (S.gsp_s[1] - S.gsp_s[0]) * C) S.gsl = D.gslot[S.gsp_s[0] + t / C];
   __syncthreads();
   TSTAMP(S, 7);
-  if (CS != C && ch0 > 0 && a.stagger > 0) {
-    // chain-split: the chains' phases out of step (identical work per phase
-    // would keep them in lockstep, contending for the CU at the same time)
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < (unsigned long long)ch0 * (unsigned)a.stagger) __builtin_amdgcn_s_sleep(4);
-  }
   if (DB) {
     for (int ph = 0; ph < S.nph; ph += 2) {
-      tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH, CS>(D, a, sh, S, ph, A, B, GA, GB);
-      if (ph + 1 < S.nph) tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH, CS>(D, a, sh, S, ph + 1, B, A, GB, GA);
+      tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH>(D, a, sh, S, ph, A, B, GA, GB);
+      if (ph + 1 < S.nph) tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH>(D, a, sh, S, ph + 1, B, A, GB, GA);
     }
   } else if (IB) {
     for (int ph = 0; ph < S.nph; ++ph) tile_phase_ib<C, NT, RMAX, GMAX, PROBE, SH>(D, a, sh, S, ph, A, GA);
   } else {
-    for (int ph = 0; ph < S.nph; ++ph) tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH, CS>(D, a, sh, S, ph, A, A, GA, GA);
+    for (int ph = 0; ph < S.nph; ++ph) tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH>(D, a, sh, S, ph, A, A, GA, GA);
   }
   }  // !XW
   // r of the tile's local rows back to global memory: the next call can start
@@ -1568,12 +1548,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
     double b0[C];
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {
-      if constexpr (CS == C) {
-        fld[ch] = a.field.p[ch];
-      } else {  // chain-split (C == 1): this workgroup's chain
-        static_assert(kMaxChains == 4, "the chain's field pointer is picked by selects");
-        fld[ch] = ch0 == 0 ? a.field.p[0] : ch0 == 1 ? a.field.p[1] : ch0 == 2 ? a.field.p[2] : a.field.p[3];
-      }
+      fld[ch] = a.field.p[ch];
       b0[ch] = D.scal[ch].beta0;
     }
     const int x0 = S.batch_s[0].w, x1 = S.batch_s[nbt - 1].w + S.batch_s[nbt - 1].z;
@@ -1590,7 +1565,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
         d[u] = xs < x1 ? a.slot_dpos[xs] : -1;
 #pragma unroll
         for (int ch = 0; ch < C; ++ch)
-          w[u][ch] = (xs < x1 && ((a.chain_mask >> ch) & 1)) ? D.w_slot[(size_t)xs * CS + ch] : 0.0;
+          w[u][ch] = (xs < x1 && ((a.chain_mask >> ch) & 1)) ? D.w_slot[(size_t)xs * C + ch] : 0.0;
       }
 #pragma unroll
       for (int u = 0; u < kTailU; ++u)
@@ -1607,7 +1582,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
 #pragma unroll
     for (int u = 0; u < kTailU; ++u) {
       if (row[u] < 0) continue;
-      double* rg = const_cast<double*>(D.r) + (size_t)row[u] * CS;
+      double* rg = const_cast<double*>(D.r) + (size_t)row[u] * C;
 #pragma unroll
       for (int ch = 0; ch < C; ++ch) rg[ch] = S.r_s[tile_r_index<C, CM>(lr + u * NT, ch, S.RS)];
     }
@@ -1620,15 +1595,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
 
 template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int RG, int IB, int XW>
 __global__ __launch_bounds__(NT) void sweep_tiles_kernel(TileDev D0, TileLaunch a, TileShard sh) {
-  sweep_tiles_body<C, NT, RMAX, GMAX, DB, PROBE, SH, RG, IB, C, XW>(D0, a, sh);
-}
-
-// chain-split: CS one-chain workgroups per tile, CS per CU (CS waves of
-// NT / 64 per SIMD: the register budget of that occupancy)
-template <int CS, int NT, int RMAX, int GMAX>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(CS * NT / 256, CS * NT / 256)))
-void sweep_tiles_cs_kernel(TileDev D0, TileLaunch a) {
-  sweep_tiles_body<1, NT, RMAX, GMAX, 0, 0, 0, 0, 0, CS>(D0, a, TileShard());
+  sweep_tiles_body<C, NT, RMAX, GMAX, DB, PROBE, SH, RG, IB, XW>(D0, a, sh);
 }
 #undef TSTAMP
 
@@ -1728,35 +1695,6 @@ static hipError_t launch_tiles_nt(hipStream_t st, const TileDev& D, const TileLa
     case 2: return launch_tiles_c<2, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ);
     case 3: return launch_tiles_c<3, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ);
     case 4: return launch_tiles_c<4, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ);
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// chain-split launch (256-thread tiles, one chain per workgroup, D.C per CU)
-template <int CS>
-static hipError_t launch_tiles_cs(hipStream_t st, const TileDev& D, const TileLaunch& a, int lds, int* occ) {
-  constexpr int NT = 256;
-  auto k = sweep_tiles_cs_kernel<CS, NT, tile_rmax_cs(NT), tile_gmax(NT)>;
-  // LDS floor: at most CS workgroups per CU
-  const int floor = kTileCuLds / (CS + 1) + 64;
-  lds = lds < floor ? floor : lds;
-  if (lds * CS > kTileCuLds) return hipErrorInvalidValue;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  if (e != hipSuccess) return e;
-  if (occ) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(k), NT, lds);
-  hipLaunchKernelGGL(tile_call_bump_kernel, dim3(1), dim3(1), 0, st, D.ctl);
-  hipLaunchKernelGGL(k, dim3(D.T * CS), dim3(NT), lds, st, D, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_sweep_tiles_cs(hipStream_t st, const TileDev& D, const TileLaunch& a, int max_rows, int NT,
-                                 int max_batches, int max_gslots, int* occ) {
-  if (NT != 256 || D.rg || D.batch_split || D.dbg) return hipErrorInvalidValue;
-  const int lds = tile_lds_bytes(max_rows, 1, NT, D.K, max_batches, max_gslots);
-  switch (D.C) {
-    case 2: return launch_tiles_cs<2>(st, D, a, lds, occ);
-    case 3: return launch_tiles_cs<3>(st, D, a, lds, occ);
-    case 4: return launch_tiles_cs<4>(st, D, a, lds, occ);
     default: return hipErrorInvalidValue;
   }
 }

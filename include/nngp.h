@@ -111,7 +111,7 @@ typedef struct {
   int tile_ghost_pass;       /* tile engine: ghost cells a (tile, colour) applies per register pass */
   int tile_ghost_cells_max;  /* tile engine: most ghost cells of one (tile, colour) */
   int tile_r_global;         /* tile engine: 1 = the tiles' r in global memory (layout beyond the LDS) */
-  int tile_chain_split;      /* tile engine: 1 = one workgroup per (chain, tile), the chains of a tile on one CU */
+  int tile_chain_split;      /* always 0: the chain-split tile launches were removed (the field keeps the layout) */
   int tile_resident_per_cu;  /* tile engine: workgroups of its kernel resident per CU at once (occupancy query);
                                 the persistent launch needs tiles <= this x CUs, else the colour engine runs */
   int engine_fallback;       /* why not the tile engine: 0 = it runs, 1 = layout unsuitable (LDS, shape),

@@ -327,7 +327,7 @@ def test_sweep_layout_refuses_column_longer_than_a_chunk(layout_check_exe, n, m,
                                                       (4000, 10, 3, 64, 8, 7), (6000, 5, 2, 256, 8, 0)])
 def test_tile_layout_refuses_column_longer_than_a_batch(tile_check_exe, n, m, chains, nt, rmax, waves):
     """build_tile_layout at H = NT x RMAX + 1 (4097 classic, 3585
-    exchange-wave, 513 wave-local, 2049 chain-split cells): returns false
+    exchange-wave, 513 wave-local, 2049 cells): returns false
     with its message; at H = NT x RMAX the layout is built and the emulation
     passes (the cap itself is a legal column)."""
     import subprocess

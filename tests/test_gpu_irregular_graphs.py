@@ -24,7 +24,7 @@ named), none widened for these graphs:
       (test_mh_building_blocks)
   beta_0 statistics (1'B'B1, 1'B'Bf) ........... rtol 1e-10
       (test_beta0_stats_reuses_loglik_pass_and_invalidates)
-  batched vs single chain, r global vs LDS, chain-split vs joint, the ranks of
+  batched vs single chain, r global vs LDS, the ranks of
   a shard vs one rank, the solve plans among each other ... bitwise.
 The hub location itself is held to the sweep bar like every other location:
 it stays at 5e-7 of it or less, so the summation bound H 2^-53 sum|terms| of
@@ -348,26 +348,20 @@ def test_hub_column_r_global_equals_lds_bitwise(P, O, engine, monkeypatch):
     _check_context(P, O, "e-tiles-1chain-r-lds-H1000", "hub1000", prob, 1, exp(0))
 
 
-def test_hub_column_chain_split_equals_joint_bitwise(P, O, engine, monkeypatch):
-    """(e) tiles, 2 chains, H = 1000: chain-split launches (256-thread tiles,
-    one workgroup per (chain, tile)) == joint tiles cut into the same
-    2048-cell batches, bitwise, after two calls (as
-    test_tile_engine_chain_split_equals_joint_bitwise on uniform graphs); the
-    joint side matches the oracle."""
+def test_hub_column_256_thread_tiles_match_oracle(P, O, engine, monkeypatch):
+    """(e) tiles, 2 chains, H = 1000: 256-thread tiles cut into 2048-cell
+    batches (as test_tile_engine_chain_split_equals_joint_bitwise on uniform
+    graphs) match the oracle."""
     if engine != "tiles-default":
         pytest.skip("sets the engine itself")
     prob = hub_problem(P, 6000, 5, 1000, 3)
-    base = {"NNGP_TILES": "24", "NNGP_TILE_NT": "256", "NNGP_TILE_BATCH_CELLS": "2048"}
+    env = {"NNGP_TILES": "24", "NNGP_TILE_NT": "256", "NNGP_TILE_BATCH_CELLS": "2048", "NNGP_TILE_CHAINS": "joint"}
 
-    def exp(split):
-        def expect(info):
-            assert info["sweep_engine"] == 1 and info["tile_chain_split"] == split, info["engine_note"]
-            assert info["max_collen"] == 1000, info
-        return expect
-    envs = [dict(base, NNGP_TILE_CHAINS="joint"), dict(base, NNGP_TILE_CHAINS="split")]
-    _bitwise_pair(P, monkeypatch, prob, 2, envs, [exp(0), exp(1)], "e-tiles-2chains-chain-split-H1000")
-    _set_env(monkeypatch, **envs[0])
-    _check_context(P, O, "e-tiles-2chains-joint-H1000", "hub1000", prob, 2, exp(0))
+    def expect(info):
+        assert info["sweep_engine"] == 1 and info["tile_chain_split"] == 0, info["engine_note"]
+        assert info["max_collen"] == 1000, info
+    _set_env(monkeypatch, **env)
+    _check_context(P, O, "e-tiles-2chains-joint-H1000", "hub1000", prob, 2, expect)
 
 
 # ---------------------------------------------------------------- refusals

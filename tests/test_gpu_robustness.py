@@ -12,6 +12,8 @@ MI355X).
 2. A tile timeout is reported by the next host sync however many sweep calls
    were enqueued after it (the sticky timeout word, tiles.hip
    tile_call_bump_kernel): injected after the first of two async calls.
+3. The switch of the removed chain-split tile launches
+   (NNGP_TILE_CHAINS=split) fails context creation instead of being ignored.
 
 Tolerance: tri solve vs the oracle rtol 1e-9, atol 1e-10 (as
 tests/test_gpu_parity.py); ticket order vs static order bitwise (same
@@ -164,3 +166,27 @@ def test_tile_timeout_survives_a_later_async_call(P, monkeypatch):
         ctx.sweep_chains(2, [0.0], [0.0], [-0.5], [3], [4])
         f = ctx.get_field()
         assert np.isfinite(f).all()
+
+
+def test_removed_chain_split_switch_is_an_error(P, monkeypatch):
+    """The chain-split launches were removed: their switch makes context
+    creation fail (NNGP_ERR_ARG, a message saying so) instead of being
+    ignored, and a context created afterwards without the switch runs the
+    tile engine and sweeps."""
+    for v in ("NNGP_ENGINE", "NNGP_TILES", "NNGP_TILE_CHAINS"):
+        monkeypatch.delenv(v, raising=False)
+    n, m = 3000, 5
+    locs, NN, col, lm, y = make_problem(P, n, m, seed=96)
+    monkeypatch.setenv("NNGP_TILE_CHAINS", "split")
+    with pytest.raises(P.NNGPError, match="removed") as e:
+        P.ChainContext(locs, NN, col, lm, y, device=0)
+    assert e.value.status == 1, e.value  # NNGP_ERR_ARG
+    monkeypatch.delenv("NNGP_TILE_CHAINS")
+    with P.ChainContext(locs, NN, col, lm, y, device=0) as ctx:
+        assert ctx.info["sweep_engine"] == 1, ctx.info
+        ctx.factor(0, "exponential_isotropic", [1.0, 0.08, 0.0])
+        ctx.set_field(np.zeros(n))
+        ctx.set_mu(None, 0.0)
+        ctx.sweep_chains(1, [0.0], [0.0], [-0.5], [3], [0])
+        f = ctx.get_field()
+        assert np.isfinite(f).all() and np.abs(f).max() > 0
