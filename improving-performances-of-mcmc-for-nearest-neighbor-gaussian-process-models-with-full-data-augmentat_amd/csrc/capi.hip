@@ -109,6 +109,7 @@ struct nngp_ctx {
   std::string err;
   SweepLayout lay;
   std::vector<int> dpos;   // loc -> device row (== lay.rpos)
+  std::vector<int> rloc;   // device row -> loc
   std::vector<int> level_ptr, level_rows;
   ChainState ch[kMaxChains];
   // device buffers
@@ -126,6 +127,7 @@ struct nngp_ctx {
   double2* dr_d = nullptr;
   int* slot_dpos_d = nullptr;
   int* dpos_d = nullptr;          // loc -> device row, on the device
+  int* rloc_d = nullptr;          // device row -> loc (the factor's failing-row number is a location)
   double* stage_h = nullptr;      // pinned n-double staging for field-sized copies
   double* mu_stage_h = nullptr;   // pinned n_obs-double staging of set_mu
   hipEvent_t mu_stage_ev = nullptr;
@@ -590,7 +592,7 @@ void nngp_ctx_destroy(nngp_ctx* c) {
                              c->r_d, c->level_rows_d, c->obs_ptr_d, c->obs_idx_d, c->ysum_d, c->lm_d, c->y_d, c->tmp_d,
                              c->tmp2_d, c->partials_d, c->res_d, c->z_d, c->scal_d, c->dbg_d,
                              c->chunk_first_d, c->loc_rank_d, c->pairs_d, c->level_ptr_d, c->zbuf_d, c->ent_pos_d, c->start_mask_d,
-                             c->dpos_d, c->perm_d, c->tb_d, c->tb_ptr_d, c->cell_pk_d, c->cell_src_d,
+                             c->dpos_d, c->rloc_d, c->perm_d, c->tb_d, c->tb_ptr_d, c->cell_pk_d, c->cell_src_d,
                              c->cell_val_d, c->gcell_d, c->gsrc_d, c->gval_d, c->gptr_d, c->rorder_d, c->gslot_d, c->gslot_ptr_d, c->nb_ptr_d, c->nb_d,
                              c->erow_ptr_d, c->erow_d, c->dwx_d, c->ctl_d, c->tdbg_d, c->sg_row_d,
                              c->sg_recv_d, c->sg_src_d, c->sg_val_d, c->xbuf_d, c->sp_pairs_d, c->tri_tmo_d};
@@ -992,6 +994,7 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
   CK(dalloc(&c->dr_d, NS * C));
   CK(dalloc(&c->slot_dpos_d, NS));
   CK(dalloc(&c->dpos_d, n));
+  CK(dalloc(&c->rloc_d, n));
   CK(dalloc(&c->perm_d, n));
   CK(hipHostMalloc((void**)&c->stage_h, sizeof(double) * n, hipHostMallocDefault));
   CK(dalloc(&c->loc_rank_d, n));
@@ -1175,6 +1178,9 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
   CK(hipMemsetAsync(c->w_slot_d, 0, sizeof(double) * NS * C, c->st));
   CK(upload(c->slot_dpos_d, slot_dpos.data(), NS, c->st));
   CK(upload(c->dpos_d, dp.data(), n, c->st));
+  c->rloc.assign(n, 0);
+  for (int i = 0; i < n; ++i) c->rloc[dp[i]] = i;
+  CK(upload(c->rloc_d, c->rloc.data(), n, c->st));
   {
     // normals: compact rank of each location; pair p = (2p, 2p+1) is generated
     // by the colour of 2p, pairs ordered by the compact rank of 2p
@@ -1374,7 +1380,7 @@ static int factor_enqueue(nngp_ctx* c, int k, int which, int covfun, const doubl
   HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->fail_d + k), INT_MAX, 1, c->st));
   S.lgen[which] = ++c->gen;
   HIPCHK(c, launch_factor(c->st, fam, var, nug, nu, c->sc_d, use_ds, c->nn_d, c->n, c->b, S.linv_d[which],
-                          c->fail_d + k));
+                          c->fail_d + k, c->rloc_d));
   return NNGP_OK;
 }
 
@@ -1413,6 +1419,7 @@ static int factor_enqueue_chains(nngp_ctx* c, int mask, int which, int covfun, c
     J.nugget[j] = nug;
     J.linv[j] = c->ch[k].linv_d[which];
     J.fail[j] = c->fail_d + k;
+    J.row_loc = c->rloc_d;
   }
   if (cnt < 2 || off || sphere || !same) {
     for (int k = 0; k < c->C; ++k)

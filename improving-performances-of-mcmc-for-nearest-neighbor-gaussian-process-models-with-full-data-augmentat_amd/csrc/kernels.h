@@ -85,10 +85,12 @@ hipError_t launch_scale_coords(hipStream_t st, int covfun, const double* cp, int
                                const double* locs_rm, int n, int d, double* sc, int ds_stride);
 
 // Vecchia factor: Linv (row-major n x b) from scaled coords.  fail: device int
-// (0 = ok, else 1 + first failing row; atomicMin semantics).
+// (INT_MAX = ok, else 1 + the first failing row; atomicMin semantics), in the
+// numbering of row_loc (row -> the number to report: the caller's location
+// order when the rows are stored in another one; nullptr: the row itself).
 hipError_t launch_factor(hipStream_t st, int family, double var, double nugget, double nu,
                          const double* sc, int ds, const int* nn, int n, int b, double* linv,
-                         int* fail);
+                         int* fail, const int* row_loc = nullptr);
 
 // the factors of up to kMaxChains chains (one covariance family) in ONE
 // launch of each of the two kernels: scaled coordinates of every job (and its
@@ -106,6 +108,7 @@ struct FactorJobs {
   double* sc[kMaxChains];                   // per-job scaled coordinates (n x ds)
   double* linv[kMaxChains];
   int* fail[kMaxChains];
+  const int* row_loc = nullptr;             // numbering of the failure flags (launch_factor)
 };
 hipError_t launch_factor_jobs(hipStream_t st, int family, double nu, const FactorJobs& J,
                               const double* locs_rm, int n, int d, int ds, const int* nn, int b);

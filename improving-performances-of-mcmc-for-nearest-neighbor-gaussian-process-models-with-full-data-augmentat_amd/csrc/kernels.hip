@@ -270,7 +270,7 @@ hipError_t launch_scale_coords(hipStream_t st, int covfun, const double* cp, int
 template <int BM, int FAM, int DS, int V, class XA>
 __device__ __forceinline__ void factor_row(const XA& xa, int bs, int i, double rsv, double nugget, int b,
                                            const double* __restrict__ tab, double* __restrict__ linv,
-                                           int* __restrict__ fail) {
+                                           int* __restrict__ fail, const int* __restrict__ row_loc) {
   constexpr int T = BM * (BM + 1) / 2;
   double L[T];
   double inv[BM];
@@ -327,7 +327,7 @@ __device__ __forceinline__ void factor_row(const XA& xa, int bs, int i, double r
     for (int q = r + 1; q < BM; ++q) s -= L[q * (q + 1) / 2 + r] * x[q];
     x[r] = s * inv[r];
   }
-  if (bad) atomicMin(fail, i + 1);
+  if (bad) atomicMin(fail, (row_loc ? row_loc[i] : i) + 1);
 #pragma unroll
   for (int j = 0; j < BM; ++j)
     if (j < b) linv[(size_t)i * b + j] = (j < bs) ? x[BM - 1 - j] * rsv : 0.0;
@@ -409,7 +409,8 @@ __global__ __launch_bounds__(64) void factor_kernel(FactorJobs J, double nu, dou
     load_nn_row<BM>(nx, nn, i2, n, b);
     if (i < n)
       factor_row<BM, FAM, DS, V>([&](int r, int k) { return X[r][k]; }, bs, i, rsqrt_pos(job_pick(J.var, jc)),
-                                 job_pick(J.nugget, jc), b, tab, job_pick(J.linv, jc), job_pick(J.fail, jc));
+                                 job_pick(J.nugget, jc), b, tab, job_pick(J.linv, jc), job_pick(J.fail, jc),
+                                 J.row_loc);
 #pragma unroll
     for (int r = 0; r < BM; ++r)
 #pragma unroll
@@ -449,7 +450,8 @@ template <int BM, int FAM, int DS>
 __global__ __launch_bounds__(64) void factor_pair_kernel(double var, double nugget, double nu, double norm,
                                                         const double* __restrict__ sc,
                                                         const int* __restrict__ nn, int n, int b,
-                                                        double* __restrict__ linv, int* __restrict__ fail) {
+                                                        double* __restrict__ linv, int* __restrict__ fail,
+                                                        const int* __restrict__ row_loc) {
   static_assert(BM % 2 == 0, "lane pairs: even block size");
   constexpr int H = BM / 2;            // points / columns per lane
   constexpr int TH = H * (H + 1);      // owned entries of the packed lower triangle: sum_t ceil((t+1)/2)
@@ -581,7 +583,7 @@ __global__ __launch_bounds__(64) void factor_pair_kernel(double var, double nugg
       x[r] = ((r & 1) == j) ? mine : other;
     }
     if (i < n) {
-      if (bad) atomicMin(fail, i + 1);
+      if (bad) atomicMin(fail, (row_loc ? row_loc[i] : i) + 1);
 #pragma clang loop unroll(full)
       for (int k = 0; k < H; ++k) {
         const int c = 2 * k + j;  // output column
@@ -717,7 +719,7 @@ __global__ __launch_bounds__(256) void factor_lanes_kernel(FactorJobs J, const i
     }
     // reduce the failure flag of the row (any lane's pivot) -- every lane
     // saw the same broadcast pivots, so lane 15's flag is the row's
-    if (bad && q == BM - 1) atomicMin(job_pick(J.fail, jb), i + 1);
+    if (bad && q == BM - 1) atomicMin(job_pick(J.fail, jb), (J.row_loc ? J.row_loc[i] : i) + 1);
     if (c < b) job_pick(J.linv, jb)[(size_t)i * b + c] = valid ? xr * rsqrt_pos(job_pick(J.var, jb)) : 0.0;
   }
 }
@@ -731,7 +733,8 @@ template <int FAM, int DS>
 __global__ __launch_bounds__(64) void factor_kernel_rt(double var, double nugget, double nu, double norm,
                                                       const double* __restrict__ sc,
                                                       const int* __restrict__ nn, int n, int b,
-                                                      double* __restrict__ linv, int* __restrict__ fail) {
+                                                      double* __restrict__ linv, int* __restrict__ fail,
+                                                      const int* __restrict__ row_loc) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
   int bs = b;
@@ -775,11 +778,11 @@ __global__ __launch_bounds__(64) void factor_kernel_rt(double var, double nugget
     for (int q = r + 1; q < bs; ++q) s -= L[q * (q + 1) / 2 + r] * x[q];
     x[r] = s * inv[r];
   }
-  if (bad) atomicMin(fail, i + 1);
+  if (bad) atomicMin(fail, (row_loc ? row_loc[i] : i) + 1);
   for (int j = 0; j < b; ++j) linv[(size_t)i * b + j] = (j < bs) ? x[bs - 1 - j] : 0.0;
 }
 
-#define NNGP_FACTOR_ARGS var, nugget, nu, norm, sc, nn, n, b, linv, fail
+#define NNGP_FACTOR_ARGS var, nugget, nu, norm, sc, nn, n, b, linv, fail, row_loc
 // workgroups of a grid-stride kernel: NNGP_FACTOR_GRID (default 2) x the
 // resident one-wave workgroups of the current device, at most the row
 // groups.  Twice resident measured best at n = 1e6 (0.350 vs 0.354 ms at 1x,
@@ -831,7 +834,8 @@ static hipError_t launch_factor_lanes(hipStream_t st, int family, int ds, const 
 
 template <int BM, int FAM, int DS>
 static hipError_t launch_factor_one(hipStream_t st, double var, double nugget, double nu, double norm,
-                                    const double* sc, const int* nn, int n, int b, double* linv, int* fail) {
+                                    const double* sc, const int* nn, int n, int b, double* linv, int* fail,
+                                    const int* row_loc) {
   if (BM <= 16 && factor_lanes_on()) {
     FactorJobs J;
     J.n_jobs = 1;
@@ -840,6 +844,7 @@ static hipError_t launch_factor_one(hipStream_t st, double var, double nugget, d
     J.sc[0] = const_cast<double*>(sc);
     J.linv[0] = linv;
     J.fail[0] = fail;
+    J.row_loc = row_loc;
     return launch_factor_lanes(st, FAM, DS, J, nn, n, b);
   }
   // NNGP_FACTOR_PAIR=1: the lane-pair kernel (opt-in: measured slower)
@@ -859,6 +864,7 @@ static hipError_t launch_factor_one(hipStream_t st, double var, double nugget, d
   J.sc[0] = const_cast<double*>(sc);
   J.linv[0] = linv;
   J.fail[0] = fail;
+  J.row_loc = row_loc;
   const auto kern = factor_kernel<BM, FAM, DS, 0>;
   const int g = resident_grid(reinterpret_cast<const void*>(kern), (n + 63) / 64);
   hipLaunchKernelGGL(kern, dim3(g), dim3(64), 0, st, J, nu, norm, nn, n, b);
@@ -887,7 +893,7 @@ static hipError_t launch_factor_jobs_bm(hipStream_t st, int ds, double nu, const
 template <int BM, int FAM>
 static hipError_t launch_factor_ds(hipStream_t st, int ds, double var, double nugget, double nu,
                                    double norm, const double* sc, const int* nn, int n, int b,
-                                   double* linv, int* fail) {
+                                   double* linv, int* fail, const int* row_loc) {
   switch (ds) {
     case 2: return launch_factor_one<BM, FAM, 2>(st, NNGP_FACTOR_ARGS);
     case 3: return launch_factor_one<BM, FAM, 3>(st, NNGP_FACTOR_ARGS);
@@ -900,7 +906,7 @@ static hipError_t launch_factor_ds(hipStream_t st, int ds, double var, double nu
 template <int FAM>
 static hipError_t launch_factor_rt(hipStream_t st, int ds, double var, double nugget, double nu,
                                    double norm, const double* sc, const int* nn, int n, int b,
-                                   double* linv, int* fail) {
+                                   double* linv, int* fail, const int* row_loc) {
   int g = (n + 63) / 64;
   switch (ds) {
     case 2: hipLaunchKernelGGL((factor_kernel_rt<FAM, 2>), dim3(g), dim3(64), 0, st, NNGP_FACTOR_ARGS); break;
@@ -913,7 +919,7 @@ static hipError_t launch_factor_rt(hipStream_t st, int ds, double var, double nu
 
 hipError_t launch_factor(hipStream_t st, int family, double var, double nugget, double nu,
                          const double* sc, int ds, const int* nn, int n, int b, double* linv,
-                         int* fail) {
+                         int* fail, const int* row_loc) {
   double norm = 0.0;
   if (b > kBMaxRt || b < 1) return hipErrorInvalidValue;
   if (family == 2) {
@@ -963,7 +969,8 @@ hipError_t launch_factor_jobs(hipStream_t st, int family, double nu, const Facto
                                     : launch_factor_jobs_bm<21, 1>(st, ds, nu, J, nn, n, b);
   }
   for (int j = 0; j < J.n_jobs; ++j)
-    if ((e = launch_factor(st, family, J.var[j], J.nugget[j], nu, J.sc[j], ds, nn, n, b, J.linv[j], J.fail[j])) !=
+    if ((e = launch_factor(st, family, J.var[j], J.nugget[j], nu, J.sc[j], ds, nn, n, b, J.linv[j], J.fail[j],
+                           J.row_loc)) !=
         hipSuccess)
       return e;
   return hipSuccess;

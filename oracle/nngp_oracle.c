@@ -162,7 +162,7 @@ int or_ncovparms(int covfun, int d) {
 }
 
 /* transform raw coordinates into the space where the covariance is isotropic
- * with unit range; writes up to 3 coords to out, returns dimension. */
+ * with unit range; writes up to 4 coords to out, returns dimension. */
 static int or_scaled_coords(int covfun, const double *cp, const double *x, int d, double *out) {
   switch (covfun) {
     case 0: case 4: case 8:
@@ -208,7 +208,7 @@ static double or_nugget(int covfun, const double *cp, int d) {
 /* Dense covariance matrix (column-major nloc x nloc) of locs (nloc x d,
  * column-major, leading dimension ld). */
 void or_covmat(int covfun, const double *cp, const double *locs, int nloc, int d, int ld, double *C) {
-  double a[3], b[3], xa[8], xb[8];
+  double a[4], b[4], xa[8], xb[8];  /* d <= 4 (nngp_ctx_create's limit) */
   for (int i = 0; i < nloc; ++i) {
     for (int k = 0; k < d; ++k) xa[k] = locs[i + (size_t)k * ld];
     int dd = or_scaled_coords(covfun, cp, xa, d, a);
