@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "nngp_factor_chains", "nngp_loglik_chains", "nngp_field_response_ratio_chains",
     "nngp_sum_squared_residuals_chains", "nngp_loglik_pair_chains",
     "nngp_ancillary_step_chains", "nngp_sufficient_step_chains",
-    "nngp_summary", "nngp_summary_stats",
+    "nngp_summary", "nngp_summary_stats", "nngp_predict_field", "nngp_predict_stats",
 )
 SHARD_ID_BYTES = 128  # NNGP_SHARD_ID_BYTES
 IPC_HANDLE_BYTES = 192  # NNGP_IPC_HANDLE_BYTES
@@ -146,6 +146,11 @@ def _load():
                                C.c_int, _dp]
     L.nngp_summary_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong),
                                      C.POINTER(C.c_int)]
+    L.nngp_predict_field.argtypes = [C.c_int, _dp, C.c_int, C.c_int, C.c_int, _ip, C.c_int, C.c_int, _dp, C.c_int,
+                                     C.c_int, C.c_int, _vp, _vp, C.c_longlong, _vp, _vp, _vp, _vp, C.c_uint64, _vp,
+                                     C.c_int, _vp, C.POINTER(C.c_int)]
+    L.nngp_predict_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     return L
 
 

@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "rec_stream.h"
 #include "summary.h"
+#include "predict.h"
 
 using namespace nngp;
 
@@ -258,6 +259,7 @@ constexpr int kTileTarget = 2048;  // locations per tile (default tile count: n 
 
 thread_local std::string g_err;
 thread_local SummaryStats g_summary_stats;  // of this thread's last successful nngp_summary
+thread_local PredictStats g_predict_stats;  // of this thread's last successful nngp_predict_field
 
 int fail_hip(nngp_ctx* c, hipError_t e, const char* what) {
   std::string m = std::string(what) + ": " + hipGetErrorString(e);
@@ -3142,6 +3144,51 @@ int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_byt
   if (kernel_ms) *kernel_ms = g_summary_stats.kernel_ms;
   if (staged_bytes) *staged_bytes = g_summary_stats.staged_bytes;
   if (chunk_cols) *chunk_cols = g_summary_stats.chunk_cols;
+  return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- prediction
+int nngp_predict_field(int device, const double* locs, int n, int n_pred, int d, const int* NNarray, int b,
+                       int covfun, const double* covparms, int ncovparms, int n_factors, int n_samples,
+                       const int* factor_of, const double* fields, long long field_pitch, const long long* field_row,
+                       const double* beta0, const double* log_scale, const double* z, uint64_t seed,
+                       const uint64_t* counter, int sample_batch, double* out, int* fail_row) {
+  if (fail_row) *fail_row = 0;
+  if (!locs || !NNarray || !covparms || !factor_of || !fields || !field_row || !beta0 || !log_scale || !out ||
+      (!z && !counter))
+    return fail_msg(nullptr, NNGP_ERR_ARG, "predict_field: null argument (z == NULL needs counter)");
+  if (n < 1 || n_pred < 1 || (long long)n + n_pred > INT_MAX || d < 1 || d > 4 || b < 1 || b > kPredictBMax ||
+      n_factors < 1 || n_samples < 1 || ncovparms < 1 || ncovparms > 8 || sample_batch < 0 || field_pitch < n)
+    return fail_msg(nullptr, NNGP_ERR_ARG,
+                    "predict_field: bad arguments (need n>=1, n_pred>=1, 1<=d<=4, 1<=b<=32, n_factors>=1, "
+                    "n_samples>=1, sample_batch>=0, field_pitch>=n)");
+  for (int s = 0; s < n_samples; ++s)
+    if (factor_of[s] < 0 || factor_of[s] >= n_factors || field_row[s] < 0)
+      return fail_msg(nullptr, NNGP_ERR_ARG, "predict_field: factor_of / field_row out of range");
+  std::vector<PredictFactor> F(n_factors);
+  for (int k = 0; k < n_factors; ++k) {
+    std::string err;
+    PredictFactor& f = F[k];
+    f.ncp = ncovparms;
+    for (int q = 0; q < 8; ++q) f.cp[q] = q < ncovparms ? covparms[(size_t)k * ncovparms + q] : 0.0;
+    f.family = covfun_family(covfun, d, f.cp, ncovparms, &f.var, &f.nugget, &f.nu, err);
+    if (f.family < 0) return fail_msg(nullptr, NNGP_ERR_ARG, "predict_field: " + err);
+  }
+  PredictArgs a{device, locs, n, n_pred, d, NNarray, b, covfun, F.data(), n_factors, n_samples, factor_of,
+                fields, field_pitch, field_row, beta0, log_scale, z, seed, counter, sample_batch, out, fail_row};
+  std::string err;
+  const int st = predict_run(a, &g_predict_stats, err);
+  return st == NNGP_OK ? NNGP_OK : fail_msg(nullptr, st, err);
+}
+
+int nngp_predict_stats(double* plan_ms, double* factor_ms, double* solve_ms, long long* staged_bytes,
+                       int* sample_batch) {
+  if (g_predict_stats.n_batches < 1) return fail_msg(nullptr, NNGP_ERR_STATE, "predict_stats: no prediction on this thread yet");
+  if (plan_ms) *plan_ms = g_predict_stats.plan_ms;
+  if (factor_ms) *factor_ms = g_predict_stats.factor_ms;
+  if (solve_ms) *solve_ms = g_predict_stats.solve_ms;
+  if (staged_bytes) *staged_bytes = g_predict_stats.staged_bytes;
+  if (sample_batch) *sample_batch = g_predict_stats.sample_batch;
   return NNGP_OK;
 }
 

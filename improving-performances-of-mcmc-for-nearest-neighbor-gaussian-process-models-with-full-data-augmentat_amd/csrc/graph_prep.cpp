@@ -965,6 +965,71 @@ void dag_levels(const int* nn, int n, int b, std::vector<int>& level_ptr, std::v
   for (int i = 0; i < n; ++i) level_rows[f[lev[i]]++] = i;
 }
 
+bool build_predict_plan(const int* NNarray, int n, int n_pred, int b, PredictPlan& P, std::string& err) {
+  if (!NNarray || n < 1 || n_pred < 1 || b < 1 || (long long)n + n_pred > std::numeric_limits<int>::max()) {
+    err = "predict plan: bad arguments";
+    return false;
+  }
+  const size_t N = (size_t)n + (size_t)n_pred;
+  P = PredictPlan();
+  P.n = n;
+  P.n_pred = n_pred;
+  P.b = b;
+  // pass 1: validate, collect the observed indices the new rows name
+  P.nn.assign((size_t)n_pred * b, -1);
+  for (int j = 0; j < b; ++j) {  // column by column: the table is column-major
+    const int* col = NNarray + (size_t)j * N + n;
+    for (int r = 0; r < n_pred; ++r) {
+      const int v = col[r];
+      if (v == std::numeric_limits<int>::min()) {
+        if (j == 0) {
+          err = "predict plan: NNarray[, 1] of a new row is NA";
+          return false;
+        }
+        continue;
+      }
+      const long long self = (long long)n + r + 1;
+      if (j == 0 ? v != self : (v < 1 || v >= self)) {
+        err = j == 0 ? "predict plan: NNarray[, 1] of a new row must be the row itself"
+                     : "predict plan: a new row names itself, a later row or an index < 1";
+        return false;
+      }
+      P.nn[(size_t)r * b + j] = v - 1;  // stacked 0-based for now
+      if (v <= n) P.support.push_back(v - 1);
+    }
+  }
+  std::sort(P.support.begin(), P.support.end());
+  P.support.erase(std::unique(P.support.begin(), P.support.end()), P.support.end());
+  P.n_support = (int)P.support.size();
+  // pass 2: compact numbering and levels (rows in order: a row's new-row
+  // neighbours precede it)
+  std::vector<int> lev(n_pred, 1);
+  int maxl = 0;
+  for (int r = 0; r < n_pred; ++r) {
+    int l = 1;
+    for (int j = 0; j < b; ++j) {
+      int& e = P.nn[(size_t)r * b + j];
+      if (e < 0) continue;
+      if (e >= n) {
+        if (j > 0) l = std::max(l, lev[e - n] + 1);
+        e = P.n_support + (e - n);
+      } else {
+        e = (int)(std::lower_bound(P.support.begin(), P.support.end(), e) - P.support.begin());
+      }
+    }
+    lev[r] = l;
+    maxl = std::max(maxl, l);
+  }
+  P.n_levels = maxl;
+  P.level_ptr.assign(maxl + 1, 0);
+  for (int r = 0; r < n_pred; ++r) P.level_ptr[lev[r]]++;
+  for (int l = 0; l < maxl; ++l) P.level_ptr[l + 1] += P.level_ptr[l];
+  P.level_rows.resize(n_pred);
+  std::vector<int> f(P.level_ptr.begin(), P.level_ptr.end() - 1);
+  for (int r = 0; r < n_pred; ++r) P.level_rows[f[lev[r] - 1]++] = r;
+  return true;
+}
+
 int tile_lds_bytes(int max_rows, int C, int NT, int K, int max_batches, int max_gslots) {
   const int rbytes = ((max_rows * C * 8 + 15) / 16) * 16;
   return rbytes + kAccSlots * C * 8 + (NT / 64) * C * 8 + 5 * C * 8 + ((max_gslots * C + 1) / 2) * 16 +

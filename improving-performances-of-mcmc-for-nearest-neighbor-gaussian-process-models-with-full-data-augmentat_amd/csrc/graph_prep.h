@@ -216,4 +216,27 @@ bool build_shard_plan(const int* nn_rowmajor, int n, int b, const int* colors, c
 void dag_levels(const int* nn_rowmajor, int n, int b, std::vector<int>& level_ptr,
                 std::vector<int>& level_rows);
 
+// Plan of the batched posterior prediction (predict.hip; nngp_predict_field of
+// include/nngp.h) from the NNarray of the N = n + n_pred stacked locations
+// (the n observed ones first).  Only the rows of the new locations are read:
+//  - support: the observed locations (0-based, sorted, unique) those rows name;
+//  - compact numbering: support entry c is compact index c, new row r (stacked
+//    row n + r) is compact index n_support + r; nn is the new rows' table in
+//    that numbering (row-major n_pred x b, -1 = NA, column 0 = the row itself);
+//  - levels: level(r) = 1 + the largest level among the new rows that row r
+//    names, 1 if it names none; level_rows holds the new rows r grouped by
+//    level (ascending r inside a level), level l = 1..n_levels at
+//    level_rows[level_ptr[l-1] .. level_ptr[l]).
+struct PredictPlan {
+  int n = 0, n_pred = 0, b = 0, n_support = 0, n_levels = 0;
+  std::vector<int> support;     // n_support
+  std::vector<int> nn;          // n_pred x b
+  std::vector<int> level_ptr;   // n_levels + 1
+  std::vector<int> level_rows;  // n_pred
+};
+// NNarray: N x b column-major, 1-based, NA = INT_MIN (R's conventions).
+// Fails (false, err set) when a new row's column 0 is not the row itself or a
+// later column names the row itself, a later row or an index < 1.
+bool build_predict_plan(const int* NNarray_colmajor, int n, int n_pred, int b, PredictPlan& P, std::string& err);
+
 }  // namespace nngp

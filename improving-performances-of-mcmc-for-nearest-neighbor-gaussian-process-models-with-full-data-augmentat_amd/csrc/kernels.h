@@ -96,7 +96,9 @@ hipError_t launch_factor(hipStream_t st, int family, double var, double nugget, 
 // launch of each of the two kernels: scaled coordinates of every job (and its
 // failure flag reset to INT_MAX), then the factor rows of all jobs as one
 // grid-stride range (one tail instead of one per chain).  Rows bitwise those
-// of launch_scale_coords + launch_factor per job.
+// of launch_scale_coords + launch_factor per job.  n_points > 0: the
+// coordinate array has n_points points (the table's n rows index into it;
+// prediction: the support set and the new locations); otherwise n of them.
 struct ScaleArgs {
   double c[8];  // covariance parameters
   int covfun;
@@ -111,7 +113,7 @@ struct FactorJobs {
   const int* row_loc = nullptr;             // numbering of the failure flags (launch_factor)
 };
 hipError_t launch_factor_jobs(hipStream_t st, int family, double nu, const FactorJobs& J,
-                              const double* locs_rm, int n, int d, int ds, const int* nn, int b);
+                              const double* locs_rm, int n, int d, int ds, const int* nn, int b, int n_points = 0);
 
 // per-row statistics of B x (x shifted): partial sums of
 // {log L[k][0], u_k^2, a_k^2, a_k*u_k} with u = B (x - shift), a = B 1.

@@ -946,10 +946,11 @@ hipError_t launch_factor(hipStream_t st, int family, double var, double nugget, 
 #undef NNGP_FACTOR_ARGS
 
 hipError_t launch_factor_jobs(hipStream_t st, int family, double nu, const FactorJobs& J,
-                              const double* locs_rm, int n, int d, int ds, const int* nn, int b) {
+                              const double* locs_rm, int n, int d, int ds, const int* nn, int b, int n_points) {
   if (J.n_jobs < 1 || J.n_jobs > kMaxChains || b < 1 || b > kBMaxRt) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(scale_coords_jobs_kernel, dim3((n + kBlock - 1) / kBlock, J.n_jobs), dim3(kBlock), 0, st, J,
-                     locs_rm, n, d, ds);
+  const int np = n_points > 0 ? n_points : n;
+  hipLaunchKernelGGL(scale_coords_jobs_kernel, dim3((np + kBlock - 1) / kBlock, J.n_jobs), dim3(kBlock), 0, st, J,
+                     locs_rm, np, d, ds);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // NNGP_FACTOR_LANES=16: the 16-lane-group kernel (b <= 16, opt-in)

@@ -4,11 +4,20 @@ Scripts/mcmc_nngp_predict.R:1-104 ("next").
 Per saved sample the field is predicted with the device factor build on the
 stacked locations and the device sparse triangular solve
 (predict.R:39-53): sd * B^{-1} c(B11 (w/sd), z).
+
+Two engines compute the same samples: ``engine="context"`` builds a
+ChainContext on the stacked locations and runs factor, SpMV and triangular
+solve per sample; ``engine="batched"`` makes one nngp_predict_field call per
+chain (include/nngp.h): the factor rows of the new locations only, and a
+level solve with the samples in the lanes (DESIGN.md "Batched prediction").
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 
+from . import _lib
 from .context import ChainContext
 from .estimate import get_summary
 from .graph import find_ordered_nn, naive_greedy_coloring
@@ -16,14 +25,34 @@ from .model import covparms
 
 
 def mcmc_nngp_predict_field(mcmc_nngp_list, predicted_locs, burn_in=0.5, n_cores=1, m=10, seed=1,
-                            device=-1, z_new=None, summary_backend="host"):
+                            device=-1, z_new=None, summary_backend="host", engine="context", rng="numpy",
+                            sample_batch=0):
     """predict.R:1-60.  ``z_new`` (optional) replaces the rnorm draws of the
     new locations (predict.R:50): z_new[k][i] = the normals of chain k's i-th
     prediction; by default they come from numpy's generator seeded ``seed``.
     ``summary_backend="hip"`` summarises the per-chain sample arrays on the
-    device (get_summary, no stacked copy); the samples are the same."""
+    device (get_summary, no stacked copy); the samples are the same.
+
+    ``engine="batched"``: one nngp_predict_field call per chain, reading
+    chain["params"]["field"] where it lies; no colouring and no ChainContext.
+    Same arguments, same samples up to rounding.  ``rng="philox"`` (batched
+    engine only) draws the normals on the device instead: sample k of a chain
+    (its ordinal among the chain's predicted samples, 0-based) uses Philox
+    counter k, and chain c (0-based) the key
+    (seed + (c + 1) * 0x9E3779B97F4A7C15) mod 2^64 -- the 64-bit golden-ratio
+    increment, so chains with one ``seed`` get distinct streams.
+    ``sample_batch`` (batched engine; 0 = automatic) is nngp_predict_field's."""
     if summary_backend not in ("host", "hip"):
         raise ValueError(f"mcmc_nngp_predict_field: summary_backend must be 'host' or 'hip', not {summary_backend!r}")
+    if engine not in ("context", "batched"):
+        raise ValueError(f"mcmc_nngp_predict_field: engine must be 'context' or 'batched', not {engine!r}")
+    if rng not in ("numpy", "philox"):
+        raise ValueError(f"mcmc_nngp_predict_field: rng must be 'numpy' or 'philox', not {rng!r}")
+    if rng == "philox" and engine != "batched":
+        raise ValueError("mcmc_nngp_predict_field: rng='philox' needs engine='batched'")
+    if engine == "batched":
+        return _predict_field_batched(mcmc_nngp_list, predicted_locs, burn_in, m, seed, device, z_new,
+                                      summary_backend, rng, sample_batch)
     L = mcmc_nngp_list
     locs = L["locs"]
     predicted_locs = np.asarray(predicted_locs, np.float64)
@@ -58,6 +87,110 @@ def mcmc_nngp_predict_field(mcmc_nngp_list, predicted_locs, burn_in=0.5, n_cores
             samples[k] = sd * x[n:]
         out.append(samples)
     ctx.close()
+    summary = get_summary(out, backend="hip", device=device) if summary_backend == "hip" \
+        else get_summary(np.vstack(out))
+    return {"predicted_locs": predicted_locs, "predicted_field_samples": out,
+            "predicted_field_summary": summary}
+
+
+def predict_field_call(locs, NN, n, covfun, covparms_rows, factor_of, fields, field_row, beta0, log_scale,
+                       z=None, seed=0, counter=None, sample_batch=0, device=-1):
+    """nngp_predict_field (include/nngp.h) on numpy arrays: ``locs`` (N x d) and
+    ``NN`` (N x b, 1-based, NA = INT_MIN) of the stacked locations, the first
+    ``n`` observed; ``fields`` a C-contiguous (rows x >= n) float64 array read
+    in place.  Returns the n_samples x n_pred samples; NNGPError carries the
+    status (``fail_row``: the stacked 1-based row of a failed factor)."""
+    N, d = locs.shape
+    n_pred = N - n
+    cp = _lib.f64(np.atleast_2d(covparms_rows))
+    factor_of = _lib.i32(factor_of)
+    n_samples = len(factor_of)
+    if not (isinstance(fields, np.ndarray) and fields.dtype == np.float64 and fields.ndim == 2
+            and fields.flags.c_contiguous):
+        fields = np.ascontiguousarray(fields, np.float64)
+    field_row = np.ascontiguousarray(field_row, np.int64)
+    beta0, log_scale = _lib.f64(beta0), _lib.f64(log_scale)
+    if len(field_row) != n_samples or len(beta0) != n_samples or len(log_scale) != n_samples:
+        raise ValueError("predict_field_call: per-sample arrays differ in length")
+    if len(field_row) and (field_row.min() < 0 or field_row.max() >= fields.shape[0]):
+        raise ValueError("predict_field_call: field_row out of range")
+    zp = cnt = None
+    if z is not None:
+        z = _lib.f64(z)
+        if z.shape != (n_samples, n_pred):
+            raise ValueError(f"predict_field_call: z must be {n_samples} x {n_pred}")
+        zp = z.ctypes.data
+    else:
+        cnt = np.ascontiguousarray(counter, np.uint64)
+        if len(cnt) != n_samples:
+            raise ValueError("predict_field_call: counter needs one entry per sample")
+    out = np.empty((max(n_samples, 0), max(n_pred, 0)))
+    fail = C.c_int(0)
+    locs_cm, nn_cm = _lib.colmajor(locs, np.float64), _lib.colmajor(NN, np.int32)
+    st = _lib.lib.nngp_predict_field(device, locs_cm, n, n_pred, d, nn_cm, NN.shape[1], _lib.COVFUNS[covfun], cp,
+                                     cp.shape[1], cp.shape[0], n_samples, factor_of.ctypes.data, fields.ctypes.data,
+                                     fields.shape[1], field_row.ctypes.data, beta0.ctypes.data, log_scale.ctypes.data,
+                                     zp, int(seed) & (2 ** 64 - 1), None if cnt is None else cnt.ctypes.data,
+                                     int(sample_batch), out.ctypes.data, C.byref(fail))
+    if st != 0:
+        try:
+            _lib.check(st)
+        except _lib.NNGPError as e:
+            e.fail_row = fail.value
+            raise
+    return out
+
+
+def predict_stats():
+    """nngp_predict_stats: the calling thread's last successful prediction."""
+    a, b, c = C.c_double(), C.c_double(), C.c_double()
+    by, sb = C.c_longlong(), C.c_int()
+    _lib.check(_lib.lib.nngp_predict_stats(C.byref(a), C.byref(b), C.byref(c), C.byref(by), C.byref(sb)))
+    return {"plan_ms": a.value, "factor_ms": b.value, "solve_ms": c.value, "staged_bytes": by.value,
+            "sample_batch": sb.value}
+
+
+PHILOX_CHAIN_MIX = 0x9E3779B97F4A7C15
+
+
+def _predict_field_batched(L, predicted_locs, burn_in, m, seed, device, z_new, summary_backend, rng, sample_batch):
+    locs = L["locs"]
+    predicted_locs = np.asarray(predicted_locs, np.float64)
+    allloc = np.vstack([locs, predicted_locs])
+    NN = find_ordered_nn(allloc, m)
+    n, n_pred = locs.shape[0], predicted_locs.shape[0]
+    covfun = L["space_time_model"]["covfun"]["stationary_covfun"]
+    sp = L["space_time_model"]["covfun"]["shape_params"]
+    first = next(iter(L["records"].values()))
+    stored = first["saved_field"]
+    stored = stored[stored > burn_in * stored.max()].astype(int)
+    gen = np.random.default_rng(seed)
+    out = []
+    for kc, chain in enumerate(L["records"].values()):
+        saved = chain["saved_field"] if "saved_field" in chain else first["saved_field"]
+        field_row = np.array([int(np.nonzero(saved == i)[0][0]) for i in stored], np.int64)
+        shapes = chain["params"]["shape"][stored - 1]
+        # predict.R:23,32: a factor is built where !duplicated(shape) marks the
+        # sample; every other sample uses the LAST factor built, also when its
+        # own shape was seen earlier and another one came in between
+        _, first_idx = np.unique(shapes, axis=0, return_index=True)
+        need = np.zeros(len(stored), bool)
+        need[first_idx] = True
+        need[:1] = True
+        factor_of = np.cumsum(need) - 1
+        rows = np.array([covparms(sp, chain["params"]["shape"][i - 1], 0.0, 1.5) for i in stored[need]], np.float64)
+        kw = {}
+        if rng == "philox":
+            kw = {"seed": (int(seed) + (kc + 1) * PHILOX_CHAIN_MIX) % 2 ** 64,
+                  "counter": np.arange(len(stored), dtype=np.uint64)}
+        elif z_new is None:
+            kw = {"z": gen.normal(size=(len(stored), n_pred))}
+        else:
+            kw = {"z": np.asarray(z_new[kc], np.float64)[:len(stored)]}
+        out.append(predict_field_call(allloc, NN, n, covfun, rows, factor_of, chain["params"]["field"], field_row,
+                                      chain["params"]["beta_0"][stored - 1, 0],
+                                      chain["params"]["log_scale"][stored - 1, 0],
+                                      sample_batch=sample_batch, device=device, **kw))
     summary = get_summary(out, backend="hip", device=device) if summary_backend == "hip" \
         else get_summary(np.vstack(out))
     return {"predicted_locs": predicted_locs, "predicted_field_samples": out,

@@ -40,6 +40,8 @@
  *   nngp_records_stream ...... records$field in host memory while the chain runs (same lines)
  *   nngp_summary ............. get_summary, Scripts/mcmc_nngp_estimate.R:1-6 (res$field,
  *                              estimate.R:88-94; predicted_field_summary, predict.R:57-58)
+ *   nngp_predict_field ....... the per-sample body of mcmc_nngp_predict_field,
+ *                              Scripts/mcmc_nngp_predict.R:39-53, for all samples of a chain
  *   nngp_spmv / nngp_tri_solve sparse_chol %*% X (update_Gaussian.R:79,147) /
  *                              Matrix::solve (initialize.R:208, predict.R:46)
  */
@@ -53,7 +55,7 @@
 extern "C" {
 #endif
 
-#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
+#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats, nngp_predict_field, nngp_predict_stats: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
 #define NNGP_SHARD_ID_BYTES 128 /* RCCL unique id */
 #define NNGP_IPC_HANDLE_BYTES 192 /* HIP IPC handles of a tile shard's granule buffer, w replica, flags */
 
@@ -370,6 +372,54 @@ int nngp_summary(int device, const double* const* blocks, const long long* block
  * call (its streams and events are gone when it returns), and
  * scripts/summary_time.py, the R wrapper and a C client all read them here. */
 int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols);
+
+/* ---------- posterior prediction at new locations (no context) ---------- */
+/* The samples of mcmc_nngp_predict_field (Scripts/mcmc_nngp_predict.R:39-53) for
+ * n_samples saved samples of one chain in one call.  The stacked factor is lower
+ * triangular and its observed rows name observed columns only, so
+ * sd B^{-1} c(B11 (w/sd), z) equals w on the observed locations and, for the new
+ * locations p = n .. N-1 in order (y = w on the observed ones, w = field - beta0),
+ *   y[p] = (sd z[p-n] - sum_{j>=1} Linv[p,j] y[NN[p,j]]) / Linv[p,0],
+ * out[s, p-n] = y[p]: only the factor rows of the new locations (the arithmetic
+ * of nngp_factor on the stacked problem) and the observed values they name are
+ * computed or moved.
+ * locs: N x d column-major, N = n + n_pred: the n ordered observed locations,
+ * then the new ones.  NNarray: N x b column-major, 1-based, NA = INT_MIN; only
+ * rows n+1..N are read (column 1 the row itself, later columns earlier rows).
+ * covparms: n_factors x ncovparms, row k = the parameters of factor k (one
+ * covfun); factor_of[s] = the 0-based factor sample s uses.  Sample s reads
+ * its field at fields + field_row[s] * field_pitch (n doubles, where they lie;
+ * field_pitch in doubles), beta0[s] and log_scale[s] (sd = exp(log_scale / 2)).
+ * Normals: z (n_samples x n_pred row-major), or z == NULL: new location i
+ * (0-based) of sample s draws the Philox / AS241 normal of (seed, counter[s], i),
+ * the value nngp_device_normals returns at [i] for sweep = counter[s].
+ * out: n_samples x n_pred row-major.  A sample's output row depends on that
+ * sample's inputs alone: not on sample_batch, the other samples or its position.
+ * Samples are processed in batches of sample_batch (0 = automatic: the largest
+ * multiple of 64 whose device buffers -- the factor rows of the batch's distinct
+ * factors, the values [support + new rows] x batch, the staged support values
+ * and the normals / output block -- stay within 1 GiB, never below 64, at most
+ * n_samples).  NNGP_ERR_CHOL: a factor row is not positive definite; *fail_row
+ * (may be NULL) = its stacked 1-based row (the first one of the first failing
+ * sample's factor), else 0.  NNGP_ERR_ARG (checked before any HIP call):
+ * a null pointer (z and counter both NULL included), n, n_pred, n_factors or
+ * n_samples < 1, d outside 1..4, b outside 1..32, factor_of out of range, bad
+ * covparms, a table whose new rows name themselves or later rows.
+ * device: HIP ordinal (-1: current); the calling thread's current device is
+ * the same after the call as before it. */
+int nngp_predict_field(int device, const double* locs, int n, int n_pred, int d,
+                       const int* NNarray, int b, int covfun, const double* covparms, int ncovparms,
+                       int n_factors, int n_samples, const int* factor_of, const double* fields,
+                       long long field_pitch, const long long* field_row, const double* beta0,
+                       const double* log_scale, const double* z, uint64_t seed, const uint64_t* counter,
+                       int sample_batch, double* out, int* fail_row);
+/* Measurement: the calling thread's last successful prediction -- host time of
+ * the plan (support set, compact table, level schedule), HIP-event times of
+ * the factor launches and of the staging + solve + output copy (each summed
+ * over the batches), the bytes staged and the batch size used.  Any pointer
+ * may be NULL.  NNGP_ERR_STATE: none yet. */
+int nngp_predict_stats(double* plan_ms, double* factor_ms, double* solve_ms, long long* staged_bytes,
+                       int* sample_batch);
 
 /* ---------- measurement ---------- */
 /* nngp_sweep_chains bracketed by HIP events on the context's stream;

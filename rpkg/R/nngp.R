@@ -105,6 +105,21 @@ nngp_get_summary <- function(samples, device = -1L) {
 }
 # HIP-event times (ms), staged bytes and chunk width of the last nngp_get_summary
 nngp_summary_stats <- function() .Call(C_nngp_summary_stats)
+# The predicted samples (n_samples x n_pred) of one chain in one call (Scripts/mcmc_nngp_predict.R:39-53):
+# locs / NNarray of the stacked locations (the n observed first), covparms one row per distinct factor,
+# factor_of (1-based row of covparms per sample), fields n_samples x n (the chain's saved fields of the
+# samples), z n_samples x n_pred normals or NULL (Philox normals of (seed, counter[s]) drawn on the device).
+# The shim takes the per-sample matrices transposed (R's column-major = the C ABI's row-major).
+nngp_predict_field <- function(locs, n, NNarray, covfun, covparms, factor_of, fields, beta_0, log_scale, z = NULL,
+                               seed = 0, counter = NULL, sample_batch = 0L, device = -1L) {
+  storage.mode(NNarray) <- "integer"
+  t(.Call(C_nngp_predict_field, as.integer(device), as.matrix(locs) + 0, as.integer(n), NNarray,
+          nngp_covfun_id(covfun), t(as.matrix(covparms)) + 0, as.integer(factor_of) - 1L, t(fields) + 0,
+          as.double(beta_0), as.double(log_scale), if (is.null(z)) NULL else t(z) + 0, as.double(seed),
+          if (is.null(counter)) NULL else as.double(counter), as.integer(sample_batch)))
+}
+# plan / factor / solve times (ms), staged bytes and batch size of the last nngp_predict_field
+nngp_predict_stats <- function() .Call(C_nngp_predict_stats)
 # r = B (field - beta0) of the selected chain as the last sweep call left it (warm-call state)
 nngp_get_sweep_r <- function(ctx) .Call(C_nngp_get_sweep_r, ctx)
 

@@ -484,6 +484,71 @@ SEXP C_nngp_summary_stats(void) {
   return out;
 }
 
+/* nngp_predict_field for one chain (Scripts/mcmc_nngp_predict.R:39-53 for all of
+ * its saved samples).  locs N x d and NNarray N x b as R holds them.  The
+ * per-sample matrices come TRANSPOSED from the R side, so that R's column-major
+ * storage is the row-major layout of the C ABI with no copy here:
+ * covparms_t ncovparms x n_factors, fields_t n x n_samples (column s = the field
+ * of sample s: the wrapper gathers the chain's saved rows with
+ * t(field[rows, ])), z_t n_pred x n_samples or NULL (Philox: seed, counter).
+ * -> n_pred x n_samples (the wrapper transposes back). */
+SEXP C_nngp_predict_field(SEXP device, SEXP locs, SEXP n, SEXP NNarray, SEXP covfun, SEXP covparms_t, SEXP factor_of,
+                          SEXP fields_t, SEXP beta0, SEXP log_scale, SEXP z_t, SEXP seed, SEXP counter,
+                          SEXP sample_batch) {
+  if (TYPEOF(locs) != REALSXP || !Rf_isMatrix(locs) || TYPEOF(NNarray) != INTSXP || !Rf_isMatrix(NNarray) ||
+      TYPEOF(covparms_t) != REALSXP || !Rf_isMatrix(covparms_t) || TYPEOF(fields_t) != REALSXP ||
+      !Rf_isMatrix(fields_t) || TYPEOF(factor_of) != INTSXP || TYPEOF(beta0) != REALSXP || TYPEOF(log_scale) != REALSXP)
+    Rf_error("nngp: predict_field: wrong argument types");
+  const int N = Rf_nrows(locs), d = Rf_ncols(locs), nobs = as_int(n), n_pred = N - nobs;
+  const int S = Rf_ncols(fields_t);
+  if (Rf_nrows(NNarray) != N || Rf_nrows(fields_t) != nobs || XLENGTH(factor_of) != S || XLENGTH(beta0) != S ||
+      XLENGTH(log_scale) != S || n_pred < 1 || S < 1)
+    Rf_error("nngp: predict_field: sizes do not match");
+  const int philox = TYPEOF(z_t) == NILSXP;
+  if (!philox && (TYPEOF(z_t) != REALSXP || !Rf_isMatrix(z_t) || Rf_nrows(z_t) != n_pred || Rf_ncols(z_t) != S))
+    Rf_error("nngp: predict_field: z must be n_pred x n_samples");
+  /* 8-byte scratch in R vectors (released with the call, also on an R error) */
+  SEXP rows_s = PROTECT(Rf_allocVector(REALSXP, S));
+  SEXP ctr_s = PROTECT(Rf_allocVector(REALSXP, S));
+  long long* rows = (long long*)(void*)REAL(rows_s);
+  uint64_t* ctr = NULL;
+  for (int s = 0; s < S; ++s) rows[s] = s;
+  if (philox) {
+    ctr = (uint64_t*)(void*)REAL(ctr_s);
+    to_u64(counter, ctr, S);
+  }
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n_pred, S));
+  int fail_row = 0;
+  const int st = nngp_predict_field(as_int(device), REAL(locs), nobs, n_pred, d, INTEGER(NNarray), Rf_ncols(NNarray),
+                                    as_int(covfun), REAL(covparms_t), Rf_nrows(covparms_t), Rf_ncols(covparms_t), S,
+                                    INTEGER(factor_of), REAL(fields_t), nobs, rows, REAL(beta0), REAL(log_scale),
+                                    philox ? NULL : REAL(z_t), (uint64_t)as_real(seed), ctr, as_int(sample_batch),
+                                    REAL(out), &fail_row);
+  if (st == NNGP_ERR_CHOL)
+    Rf_error("nngp: local covariance of stacked row %d is not positive definite (status %d)", fail_row, st);
+  check(st, NULL);
+  UNPROTECT(3);
+  return out;
+}
+
+/* the last prediction's plan / factor / solve times (ms), staged bytes and batch size */
+SEXP C_nngp_predict_stats(void) {
+  static const char* names[5] = {"plan_ms", "factor_ms", "solve_ms", "staged_bytes", "sample_batch"};
+  double v[3] = {0, 0, 0};
+  long long bytes = 0;
+  int batch = 0;
+  check(nngp_predict_stats(&v[0], &v[1], &v[2], &bytes, &batch), NULL);
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, 5));
+  SEXP nm = PROTECT(Rf_allocVector(STRSXP, 5));
+  for (int i = 0; i < 3; ++i) REAL(out)[i] = v[i];
+  REAL(out)[3] = (double)bytes;
+  REAL(out)[4] = (double)batch;
+  for (int i = 0; i < 5; ++i) SET_STRING_ELT(nm, i, Rf_mkChar(names[i]));
+  Rf_setAttrib(out, R_NamesSymbol, nm);
+  UNPROTECT(2);
+  return out;
+}
+
 SEXP C_nngp_get_sweep_r(SEXP p) {
   nngp_ctx* c = get_ctx(p);
   SEXP r = PROTECT(Rf_allocVector(REALSXP, ctx_n(c)));
@@ -749,6 +814,8 @@ static const R_CallMethodDef call_methods[] = {
     E(C_nngp_device_normals, 4),
     E(C_nngp_summary, 2),
     E(C_nngp_summary_stats, 0),
+    E(C_nngp_predict_field, 14),
+    E(C_nngp_predict_stats, 0),
     E(C_nngp_get_sweep_r, 1),
     E(C_nngp_shard_unique_id, 0),
     E(C_nngp_shard_comm_init, 2),
