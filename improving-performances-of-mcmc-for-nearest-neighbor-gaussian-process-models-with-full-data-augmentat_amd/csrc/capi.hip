@@ -755,10 +755,12 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
         delete c;
         return fail_msg(nullptr, NNGP_ERR_ARG, "NNGP_TILE_NT must be 256, 512 or 1024");
       }
-      // NNGP_TILE_SPLIT=1 (3-4 chains): interior-first layouts (kernels.hip
-      // tile_phase_ib).  Opt-in: measured 3,607 vs 2,564 us per 10-sweep
-      // launch at the headline (two batches per colour, and the next colour's
-      // stream no longer overlaps the hand-off with one register set)
+      // NNGP_TILE_SPLIT=1 (3-4 chains): interior-first layouts, on wave-local
+      // batches only (tiles.hip tile_phase_wlib; opt-in, measured slower).
+      // Their schedule on workgroup batches was removed: measured 3,607 vs
+      // 2,564 us per 10-sweep launch at the headline (two batches per colour,
+      // and the next colour's stream no longer overlaps the hand-off with one
+      // register set); asking for it is an error (below)
       const char* tsp = std::getenv("NNGP_TILE_SPLIT");
       const bool split = tile_double_buffer(n_chains, NT) == 0 && tsp && std::string(tsp) == "1";
       // a tile's own rows alone beyond the LDS: no layout to build (n = 8e6 on
@@ -795,10 +797,15 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
       // n = 1e7 one chain 284 vs 364.
       const char* twl = std::getenv("NNGP_TILE_WL");
       const bool wl_env = twl ? std::string(twl) == "1" : (n_chains >= 3 && !rg_forced);
-      // interior-first layouts run on wave-local batches (tiles.hip
-      // tile_phase_wlib) or, without the exchange wave, on workgroup batches
-      const bool xw = (!split || wl_env) && (!rg_forced || wl_env) && NT == 512 && xwm == 1;
+      const bool xw = (!rg_forced || wl_env) && NT == 512 && xwm == 1;
       const bool wl = xw && wl_env;
+      if (split && !wl) {
+        delete c;
+        return fail_msg(nullptr, NNGP_ERR_ARG,
+                        "NNGP_TILE_SPLIT=1 needs wave-local batches (512-thread exchange-wave tiles, NNGP_TILE_WL=1 "
+                        "below 3 chains or with r in global memory): the interior-first layouts on workgroup batches "
+                        "were removed");
+      }
       const int NTL = wl ? 64 : (xw ? NT - 64 : NT);  // the layout's cell threads of a batch
       if (const char* bc = std::getenv("NNGP_TILE_BATCH_CELLS"))
         rmax_l = std::max(1, std::min(rmax_l, std::atoi(bc) / NTL));

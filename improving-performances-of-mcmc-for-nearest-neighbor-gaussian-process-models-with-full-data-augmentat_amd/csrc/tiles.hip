@@ -774,132 +774,6 @@ __device__ __forceinline__ void tile_phase(const TileDev& D, const TileLaunch& a
   TLSTAMP(S, 3);
 }
 
-// One colour phase of a SPLIT layout (one register set, C >= 3): the
-// interior batches of colour c -- slots whose rows have no member of colour
-// c-1 owned by another tile -- go first, while the granules of colour c-1
-// are still in flight; then that hand-off (poll, ghost cells of c-1); then
-// the boundary batches of c.  The chain from a neighbour's draw to this
-// tile's next draw runs through the few boundary slots only; the interior
-// work covers the hand-off latency.  Per row the updates of c and c-1 may
-// land in the other order than in the colour-by-colour schedule (rounding
-// only: an interior slot never reads a row waiting for its c-1 update).
-template <int C, int NT, int RMAX, int GMAX, int PROBE, int SH>
-__device__ __forceinline__ void tile_phase_ib(const TileDev& D, const TileLaunch& a, const TileShard& sh, TileState& S,
-                                              int ph, TileBatchRegs<C, NT, RMAX>& cur, TileGhostRegs<C, GMAX>& gr) {
-  const int K = S.K, t = S.t;
-  const int s = ph / K, c = ph - s * K;
-  const unsigned epoch = (unsigned)ph + 1;
-  S.ph = ph;
-  TLSTAMP(S, 0);
-  const int phn = ph + 1;
-  const int cn = phn % K, sn = phn / K;
-  const bool has_next = phn < S.nph;
-  const bool more = has_next && S.bptr_s[cn] < S.bptr_s[cn + 1];
-  const int bfirst = S.bptr_s[c], bsplit = S.bsp_s[c], bend = S.bptr_s[c + 1];
-  const bool had_int = bsplit > bfirst, had_bnd = bend > bsplit;
-  // the hand-off of the previous colour (none at the first phase of a call)
-  const bool hp = ph > 0;
-  const int cp = hp ? (ph - 1) % K : 0;
-  const int g0 = S.gptr_s[cp], g1 = hp ? S.gptr_s[cp + 1] : g0;
-  const int gs0 = S.gsp_s[cp], nfi = hp ? (S.gsp_s[cp + 1] - gs0) * C : 0;
-  const int gsl_pref = t < nfi ? D.gslot[gs0 + t / C] : 0;
-  const bool pol = t < nfi;
-  u32x4_t gfirst;
-  // ---- 1. interior batches; after the last draw (records dead) the next
-  // batch's records, the hand-off's ghost cells and first poll go out
-  for (int bi = bfirst; bi < bsplit; ++bi) {
-    if (bi != bfirst) {
-      __syncthreads();
-      tile_load_batch<C, NT, RMAX, SH>(D, S.batch_s[bi], cur, t);
-      tile_prep_items<C, NT, RMAX>(D, a, S.sc_s, S.seed_s, s, cur, t);
-    }
-    tile_own_draw<C, NT, RMAX, PROBE, SH>(D, a, sh, S, cur, epoch);
-    const int R = cur.R;
-    if (bi + 1 == bsplit) {
-      if (had_bnd) tile_load_items<C, NT, RMAX, SH>(D, S.batch_s[bsplit], cur, t);
-      else if (more) tile_load_items<C, NT, RMAX, SH>(D, S.batch_s[S.bptr_s[cn]], cur, t);
-      if (g1 > g0) tile_load_ghosts<C, NT, GMAX>(D, g0, g1, gr, t);
-      if (pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * C + t % C) * 16), 0,
-                                                              SH ? kGranAuxSys : kGranAux);
-    }
-    tile_own_scatter<C, NT, RMAX, PROBE>(S, cur, R);
-  }
-  if (!had_int) {
-    if (g1 > g0) tile_load_ghosts<C, NT, GMAX>(D, g0, g1, gr, t);
-    if (pol) gfirst = __builtin_amdgcn_raw_buffer_load_b128(S.gran, (int)(((size_t)gsl_pref * C + t % C) * 16), 0,
-                                                            SH ? kGranAuxSys : kGranAux);
-  } else {
-    if (had_bnd) tile_load_cells<C, NT, RMAX>(D, S.batch_s[bsplit], cur, t);
-    else if (more) tile_load_cells<C, NT, RMAX>(D, S.batch_s[S.bptr_s[cn]], cur, t);
-  }
-  TLSTAMP(S, 6);
-  // ---- 2. hand-off of colour c-1: the granule of each (foreign slot, chain)
-  // until it carries epoch ph -> gdw_s; then its ghost cells
-  if (hp) {
-    const unsigned ep = (unsigned)ph;
-    for (int u0 = 0; u0 < nfi; u0 += NT) {
-      const int u = u0 + t;
-      if (u < nfi) {
-        const int x = u0 == 0 ? gsl_pref : D.gslot[gs0 + u / C];
-        const int ch = u % C;
-        const int off = (int)(((size_t)x * C + ch) * 16);
-        u32x4_t g = u0 == 0 ? gfirst
-                            : __builtin_amdgcn_raw_buffer_load_b128(S.gran, off, 0, SH ? kGranAuxSys : kGranAux);
-        double dw = 0.0;
-        for (unsigned spins = 0;; ++spins) {
-          if (g.z == ep && (g.w ^ g.x ^ g.y) == S.call) {
-            dw = __builtin_bit_cast(double, (unsigned long long)g.x | ((unsigned long long)g.y << 32));
-            if (PROBE == 2) atomicMax(S.spin_s, spins);
-            break;
-          }
-          if (S.timed_out || spins > (1u << 20) ||
-              ((spins & 1023u) == 1023u && __hip_atomic_load(S.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-            if (!S.timed_out) tile_timeout_raise(S.tmo);
-            S.timed_out = true;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-          g = __builtin_amdgcn_raw_buffer_load_b128(S.gran, off, 0, SH ? kGranAuxSys : kGranAux);
-        }
-        S.gdw_s[u] = dw;
-      }
-    }
-    __syncthreads();
-    if (PROBE == 2 && t == 0 && S.ph < kTimelinePhases) {
-      D.dbg[((size_t)S.T * kTimelinePhases + S.ph) * kTimelineSlots + 5] = *S.spin_s;
-      *S.spin_s = 0;
-    }
-    for (int gb = g0; gb < g1; gb += NT * GMAX) {
-      if (gb != g0) tile_load_ghosts<C, NT, GMAX>(D, gb, g1, gr, t);
-      tile_ghost_adds<C, GMAX>(S, gr);
-    }
-    __syncthreads();
-  } else if (had_int && had_bnd) {
-    __syncthreads();  // acc_s: every wave is done with the interior batch
-  }
-  TLSTAMP(S, 2);
-  // ---- 3. boundary batches; after the last draw the next phase's records
-  for (int bi = bsplit; bi < bend; ++bi) {
-    if (bi != bsplit) {
-      __syncthreads();
-      tile_load_batch<C, NT, RMAX, SH>(D, S.batch_s[bi], cur, t);
-    }
-    if (bi != bsplit || had_int) tile_prep_items<C, NT, RMAX>(D, a, S.sc_s, S.seed_s, s, cur, t);
-    tile_own_draw<C, NT, RMAX, PROBE, SH>(D, a, sh, S, cur, epoch);
-    const int R = cur.R;
-    if (bi + 1 == bend && more) tile_load_items<C, NT, RMAX, SH>(D, S.batch_s[S.bptr_s[cn]], cur, t);
-    tile_own_scatter<C, NT, RMAX, PROBE>(S, cur, R);
-  }
-  // ---- 4. the next phase's first batch: its cells, then its draw scalars
-  if (more) {
-    if (had_bnd) tile_load_cells<C, NT, RMAX>(D, S.batch_s[S.bptr_s[cn]], cur, t);
-    else if (!had_int) tile_load_batch<C, NT, RMAX, SH>(D, S.batch_s[S.bptr_s[cn]], cur, t);
-    tile_prep_items<C, NT, RMAX>(D, a, S.sc_s, S.seed_s, sn, cur, t);
-  }
-  __syncthreads();
-  TLSTAMP(S, 3);
-}
-
 // ---- wave-local batches (XW == 2; TileLayout::W): every own batch is ONE
 // wave's -- whole slots, 64 lanes x R cells, at most kWaveSlotsMax slots --
 // and the W cell waves run the batches of a colour side by side, wave w the
@@ -1337,10 +1211,9 @@ __device__ __forceinline__ void tile_phase_cells(const TileDev& D, const TileLau
 // read-modify-writes; the phase barriers order them for the workgroup.
 //
 // One workgroup per tile runs every chain of the context (C).  The schedule
-// of the phase loop is picked by XW and IB:
+// of the phase loop is picked by XW (and, with XW = 2, IB):
 //  XW = 0, classic tiles: every wave holds cells and polls the hand-off
-//    itself (tile_phase; DB: two batch register sets, phases alternate them;
-//    IB: tile_phase_ib on a split layout);
+//    itself (tile_phase; DB: two batch register sets, phases alternate them);
 //  XW = 1, exchange-wave tiles: the last wave runs tile_phase_xw, the other
 //    NT - 64 threads tile_phase_cells on workgroup batches (r in LDS only);
 //  XW = 2, wave-local batches: the last wave runs tile_phase_xw, every other
@@ -1352,12 +1225,14 @@ __device__ __forceinline__ void tile_phase_cells(const TileDev& D, const TileLau
 // metadata into LDS (a warm call's beta_0 shift applied on the way), the
 // epilogue writes the field of the tile's own slots and r back.
 // (A launch with one chain per workgroup, "chain-split", was measured slower
-// and removed: DESIGN.md §0, §3.)
+// and removed: DESIGN.md §0, §3.  So was the interior-first schedule on
+// workgroup batches, XW = 0 with IB: DESIGN.md §3; IB is left with XW = 2.)
 constexpr int kTailU = 4;  // slots / rows per thread and pass of the closing write-backs
 template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int RG, int IB, int XW = 0>
 __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a, const TileShard& sh) {
-  static_assert(!XW || ((!RG || XW == 2) && (!IB || XW == 2)),
-                "exchange-wave tiles: split layouts and r in global memory only with wave-local batches");
+  static_assert((!RG || !XW || XW == 2) && (!IB || XW == 2),
+                "r in global memory not on exchange-wave tiles with workgroup batches; split layouts only with "
+                "wave-local batches");
   constexpr int NTC = XW ? NT - 64 : NT;  // cell threads
   constexpr int CM = tile_r_chain_major(C, RG, SH, XW);  // r_s layout (tile_r_index)
   using BR = TileBatchRegs<C, NTC, RMAX>;
@@ -1526,8 +1401,6 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
       tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH>(D, a, sh, S, ph, A, B, GA, GB);
       if (ph + 1 < S.nph) tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH>(D, a, sh, S, ph + 1, B, A, GB, GA);
     }
-  } else if (IB) {
-    for (int ph = 0; ph < S.nph; ++ph) tile_phase_ib<C, NT, RMAX, GMAX, PROBE, SH>(D, a, sh, S, ph, A, GA);
   } else {
     for (int ph = 0; ph < S.nph; ++ph) tile_phase<C, NT, RMAX, GMAX, DB, PROBE, SH>(D, a, sh, S, ph, A, A, GA, GA);
   }
@@ -1610,14 +1483,16 @@ static hipError_t launch_tiles_c(hipStream_t st, const TileDev& D, const TileLau
   constexpr int RMAX = tile_rmax(C, NT);
   constexpr int DB = tile_double_buffer(C, NT);
   constexpr int GMAX = tile_gmax(NT);
-  // split layouts (interior first) at one register set; IB0 >= 0 pins it
-  if constexpr (IB0 < 0 && DB == 0) {
+  // split layouts (interior first) at one register set, on wave-local
+  // batches only (XW = 2, instantiated below at these NT, RG, PROBE); IB0 >= 0
+  // pins it
+  if constexpr (IB0 < 0 && DB == 0 && NT == 512 && (!RG || !PROBE)) {
     if (D.batch_split) return launch_tiles_c<C, NT, PROBE, SH, RG, 1>(st, D, a, lds, sh, grid, occ);
     return launch_tiles_c<C, NT, PROBE, SH, RG, 0>(st, D, a, lds, sh, grid, occ);
   }
   constexpr int IB = IB0 > 0 ? 1 : 0;
-  if (D.batch_split && !IB) return hipErrorInvalidValue;  // split layout: double-buffered path not for it
-  auto k = sweep_tiles_kernel<C, NT, RMAX, GMAX, DB, PROBE, SH, RG, IB, 0>;
+  if (D.batch_split && (!IB || D.xw != 2)) return hipErrorInvalidValue;  // split layout: no other path runs it
+  auto k = sweep_tiles_kernel<C, NT, RMAX, GMAX, DB, PROBE, SH, RG, IB, IB ? 2 : 0>;
   if constexpr (NT == 512 && !RG && !IB) {
     if (D.xw == 1) k = sweep_tiles_kernel<C, NT, RMAX, GMAX, DB, PROBE, SH, RG, IB, 1>;
   }

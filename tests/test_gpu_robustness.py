@@ -14,6 +14,8 @@ MI355X).
    tile_call_bump_kernel): injected after the first of two async calls.
 3. The switch of the removed chain-split tile launches
    (NNGP_TILE_CHAINS=split) fails context creation instead of being ignored.
+4. So does NNGP_TILE_SPLIT=1 where it would need the removed interior-first
+   schedule on workgroup batches (NNGP_TILE_WL=0, NNGP_TILE_XW=0).
 
 Tolerance: tri solve vs the oracle rtol 1e-9, atol 1e-10 (as
 tests/test_gpu_parity.py); ticket order vs static order bitwise (same
@@ -189,4 +191,36 @@ def test_removed_chain_split_switch_is_an_error(P, monkeypatch):
         ctx.set_mu(None, 0.0)
         ctx.sweep_chains(1, [0.0], [0.0], [-0.5], [3], [0])
         f = ctx.get_field()
+        assert np.isfinite(f).all() and np.abs(f).max() > 0
+
+
+def test_interior_first_without_wave_local_batches_is_an_error(P, monkeypatch):
+    """The interior-first schedule on workgroup batches was removed:
+    NNGP_TILE_SPLIT=1 at 3 chains with NNGP_TILE_WL=0 or NNGP_TILE_XW=0 makes
+    context creation fail (NNGP_ERR_ARG, a message saying so) instead of
+    running another schedule; at 1 chain the switch is ignored as before, and
+    with wave-local batches (the default at 3 chains) it still runs."""
+    for v in ("NNGP_ENGINE", "NNGP_TILES", "NNGP_TILE_CHAINS", "NNGP_TILE_WL", "NNGP_TILE_XW", "NNGP_TILE_NT",
+              "NNGP_TILE_R"):
+        monkeypatch.delenv(v, raising=False)
+    n, m = 3000, 5
+    locs, NN, col, lm, y = make_problem(P, n, m, seed=96)
+    monkeypatch.setenv("NNGP_TILE_SPLIT", "1")
+    for var in ("NNGP_TILE_WL", "NNGP_TILE_XW"):
+        monkeypatch.setenv(var, "0")
+        with pytest.raises(P.NNGPError, match="workgroup batches were removed") as e:
+            P.ChainContext(locs, NN, col, lm, y, device=0, n_chains=3)
+        assert e.value.status == 1, e.value  # NNGP_ERR_ARG
+        with P.ChainContext(locs, NN, col, lm, y, device=0) as ctx:
+            assert ctx.info["sweep_engine"] == 1 and "interior first" not in ctx.info["engine_note"], ctx.info
+        monkeypatch.delenv(var)
+    with P.ChainContext(locs, NN, col, lm, y, device=0, n_chains=3) as ctx:
+        assert ctx.info["sweep_engine"] == 1 and "interior first" in ctx.info["engine_note"], ctx.info
+        for k in range(3):
+            ctx.select(k)
+            ctx.factor(0, "exponential_isotropic", [1.0, 0.08, 0.0])
+            ctx.set_field(np.zeros(n))
+            ctx.set_mu(None, 0.0)
+        ctx.sweep_chains(1, [0.0] * 3, [0.0] * 3, [-0.5] * 3, [3, 4, 5], [0] * 3)
+        f = ctx.select(0).get_field()
         assert np.isfinite(f).all() and np.abs(f).max() > 0
