@@ -44,6 +44,8 @@ ABI_SYMBOLS = (
     "nngp_sum_squared_residuals_chains", "nngp_loglik_pair_chains",
     "nngp_ancillary_step_chains", "nngp_sufficient_step_chains",
     "nngp_summary", "nngp_summary_stats", "nngp_predict_field", "nngp_predict_stats",
+    "nngp_design_set", "nngp_design_mean_stats_chains", "nngp_design_interweave_stats_chains",
+    "nngp_design_commit_chains", "nngp_get_mu",
 )
 SHARD_ID_BYTES = 128  # NNGP_SHARD_ID_BYTES
 IPC_HANDLE_BYTES = 192  # NNGP_IPC_HANDLE_BYTES
@@ -151,6 +153,11 @@ def _load():
                                      C.c_int, _vp, C.POINTER(C.c_int)]
     L.nngp_predict_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
+    L.nngp_design_set.argtypes = [_vp, _vp, C.c_int, _vp, _vp, C.c_int]
+    L.nngp_design_mean_stats_chains.argtypes = [_vp, C.c_int, _dp, _dp]
+    L.nngp_design_interweave_stats_chains.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp, _ip]
+    L.nngp_design_commit_chains.argtypes = [_vp, C.c_int, _dp, _vp, _vp, _dp, _dp]
+    L.nngp_get_mu.argtypes = [_vp, _dp]
     return L
 
 

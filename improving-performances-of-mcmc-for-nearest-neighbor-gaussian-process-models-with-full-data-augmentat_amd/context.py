@@ -45,6 +45,7 @@ class ChainContext:
         self._h = h
         self._sel = 0
         self._rec_host = {}  # chain -> host array its records stream into (records_stream)
+        self.design_p, self.design_p_locs = 0, 0  # columns of the resident design (design_set)
 
     def select(self, chain: int) -> "ChainContext":
         if chain != self._sel:
@@ -293,6 +294,63 @@ class ChainContext:
         self._chk(lib.nngp_sum_squared_residuals(self._h, float(beta0), C.byref(out)))
         return out.value
 
+    # ------------------------------------------------------------ regression block
+    def design_set(self, X, first_obs=None, locs_cols=()) -> None:
+        """The design matrix of the regression block, resident for all chains:
+        X (n_obs x p, centred), first_obs (hctam_scol_1: 1-based first
+        observation of each location) and locs_cols (X$locs: 0-based columns
+        of X that are constant within a location).  X = None frees it."""
+        if X is None:
+            self._chk(lib.nngp_design_set(self._h, None, 0, None, None, 0))
+            self.design_p, self.design_p_locs = 0, 0
+            return
+        X = np.asarray(X, np.float64)
+        Xc = colmajor(X, np.float64)
+        fo = i32(first_obs)
+        cols = i32(np.asarray(locs_cols, np.int64) + 1)
+        assert X.ndim == 2 and X.shape[0] == self.n_obs and len(fo) == self.n
+        self._chk(lib.nngp_design_set(self._h, Xc.ctypes.data, X.shape[1], fo.ctypes.data,
+                                      cols.ctypes.data if len(cols) else None, len(cols)))
+        self.design_p, self.design_p_locs = X.shape[1], len(cols)
+
+    def _rows(self, a, width):
+        """per-chain rows (n_chains x width) of a per-chain matrix argument"""
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64).reshape(-1, width)
+                                                    if width else np.zeros((1, 0)), (self.n_chains, width)))
+
+    def design_mean_stats_chains(self, chain_mask: int, beta0) -> np.ndarray:
+        """-> n_chains x (p+1): crossprod(y - field[locs_match] + beta0, cbind(1, X)) per chain."""
+        out = np.zeros((self.n_chains, self.design_p + 1))
+        self._chk(lib.nngp_design_mean_stats_chains(self._h, int(chain_mask), self._vec(beta0), out.reshape(-1)))
+        return out
+
+    def design_interweave_stats_chains(self, chain_mask: int, shift, beta_locs):
+        """-> (t, gram, refreshed): t[k] = crossprod(B (field + shift + Xl beta_locs), B Xl1),
+        gram[k] = crossprod(B Xl1), refreshed[k] = B Xl1 was formed again in this call."""
+        q = self.design_p_locs + 1
+        t = np.zeros((self.n_chains, q))
+        gram = np.zeros((self.n_chains, q, q))
+        refreshed = np.zeros(self.n_chains, np.int32)
+        self._chk(lib.nngp_design_interweave_stats_chains(self._h, int(chain_mask), self._vec(shift),
+                                                          self._rows(beta_locs, q - 1).reshape(-1), t.reshape(-1),
+                                                          gram.reshape(-1), refreshed))
+        return t, gram, refreshed
+
+    def design_commit_chains(self, chain_mask: int, shift, beta_locs_old, beta_locs_new, beta0, beta) -> None:
+        """field = (field + shift + Xl beta_locs_old) - Xl beta_locs_new and
+        mu = beta0 + X beta for the chains of the mask (no host sync)."""
+        ql = self.design_p_locs
+        old = self._rows(beta_locs_old, ql).reshape(-1) if ql else None
+        new = self._rows(beta_locs_new, ql).reshape(-1) if ql else None
+        self._chk(lib.nngp_design_commit_chains(self._h, int(chain_mask), self._vec(shift),
+                                                old.ctypes.data if ql else None, new.ctypes.data if ql else None,
+                                                self._vec(beta0), self._rows(beta, self.design_p).reshape(-1)))
+
+    def get_mu(self) -> np.ndarray:
+        out = np.zeros(self.n_obs)
+        self._chk(lib.nngp_get_mu(self._h, out))
+        return out
+
     def spmv(self, which: int, X) -> np.ndarray:
         X = np.asarray(X, np.float64)
         vec = X.ndim == 1
@@ -329,7 +387,9 @@ class ChainView:
                                                      "ancillary_propose_chains", "factor_chains", "loglik_chains",
                                                      "field_response_ratio_chains", "sum_squared_residuals_chains",
                                                      "loglik_pair_chains", "ancillary_step_chains",
-                                                     "sufficient_step_chains"):
+                                                     "sufficient_step_chains", "design_set",
+                                                     "design_mean_stats_chains", "design_interweave_stats_chains",
+                                                     "design_commit_chains"):
             return attr
 
         def bound(*a, **kw):

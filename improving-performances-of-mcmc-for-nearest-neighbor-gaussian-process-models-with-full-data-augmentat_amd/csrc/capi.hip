@@ -23,6 +23,7 @@
 #include "rec_stream.h"
 #include "summary.h"
 #include "predict.h"
+#include "regress.h"
 
 using namespace nngp;
 
@@ -93,10 +94,48 @@ std::atomic<int>& tile_ctx_count(int device) {
   return counts[device & 63];
 }
 
+// The design matrix of the regression block (nngp_design_set) and what the
+// three nngp_design_* operations keep on the device: X for all chains, Xl1 =
+// cbind(1, X[first_obs, locs]) at device rows, and per chain SX = B_cur Xl1
+// with the factor generation it was formed from and its Gram matrix.
+struct Design {
+  int p = 0, q = 1;              // columns of X; columns of Xl1 (p_locs + 1)
+  double* X_d = nullptr;         // n_obs x p column-major
+  double* Xl1_d = nullptr;       // n x q column-major, device rows (q > 1)
+  double* sx_d[kMaxChains] = {}; // n x q column-major, device rows (q > 1)
+  uint64_t sx_lgen[kMaxChains] = {};  // ChainState::lgen[0] SX was formed from (0: never)
+  std::vector<double> gram[kMaxChains];  // crossprod(SX), q x q
+  double* oth_d = nullptr;       // C x n: other = field + shift + Xl beta_locs
+  double* bo_d = nullptr;        // C x n: B_cur other
+  double* part_d = nullptr;      // partials of the reductions
+  int res_stride = 0;            // doubles per chain of res_d / res_h
+  double* res_d = nullptr;       // C x res_stride
+  double* res_h = nullptr;       // pinned mirror
+  // coefficients of a call: C x (q-1) old and new beta_locs, C x p beta --
+  // staged through a pinned ring so that a commit returns before its copy ran
+  static constexpr int kRing = 4;
+  size_t coef_len = 0;
+  double* coef_d = nullptr;
+  double* coef_h = nullptr;      // pinned, kRing x coef_len
+  hipEvent_t coef_ev[kRing] = {};
+  int coef_next = 0;
+  void release() {
+    for (void* q_ : {(void*)X_d, (void*)Xl1_d, (void*)oth_d, (void*)bo_d, (void*)part_d, (void*)res_d, (void*)coef_d})
+      if (q_) hipFree(q_);
+    for (double* s : sx_d)
+      if (s) hipFree(s);
+    if (res_h) hipHostFree(res_h);
+    if (coef_h) hipHostFree(coef_h);
+    for (hipEvent_t e : coef_ev)
+      if (e) hipEventDestroy(e);
+  }
+};
+
 struct nngp_ctx {
   ~nngp_ctx() {
     if (tile_counted) tile_ctx_count(device)--;
   }
+  Design* dsg = nullptr;  // nngp_design_set
   bool tile_counted = false;  // counted in tile_ctx_count(device)
   RecordStreamer* recs = nullptr;  // record rows -> host arrays (nngp_records_stream), lazily started
   // a sweep returned without a host sync: its tile timeout word is checked
@@ -616,6 +655,10 @@ void nngp_ctx_destroy(nngp_ctx* c) {
     ptrs.insert(ptrs.end(), {s.linv_d[0], s.linv_d[1], s.field_d, s.field_prop_d, s.mu_d, s.rec_d, s.b1_d});
   }
   for (void* p : ptrs) if (p) hipFree(p);
+  if (c->dsg) {
+    c->dsg->release();
+    delete c->dsg;
+  }
   if (c->scal_h) hipHostFree(c->scal_h);
   if (c->scal_ring_h) hipHostFree(c->scal_ring_h);
   for (hipEvent_t& e : c->scal_ev)
@@ -3196,6 +3239,270 @@ int nngp_predict_stats(double* plan_ms, double* factor_ms, double* solve_ms, lon
   if (solve_ms) *solve_ms = g_predict_stats.solve_ms;
   if (staged_bytes) *staged_bytes = g_predict_stats.staged_bytes;
   if (sample_batch) *sample_batch = g_predict_stats.sample_batch;
+  return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- regression block
+// (update_Gaussian.R:77-83,145-151,226-250; kernels in regress.hip)
+static void design_free(nngp_ctx* c) {
+  if (!c->dsg) return;
+  hipStreamSynchronize(c->st);
+  c->dsg->release();
+  delete c->dsg;
+  c->dsg = nullptr;
+}
+
+int nngp_design_set(nngp_ctx* c, const double* X, int p, const int* first_obs, const int* locs_cols, int p_locs) {
+  if (!c) return NNGP_ERR_ARG;
+  if (c->shard) return fail_msg(c, NNGP_ERR_STATE, "design_set: a shard context holds no design");
+  int rc;
+  if (!X) {
+    if ((rc = set_device(c))) return rc;
+    design_free(c);
+    return NNGP_OK;
+  }
+  if (p < 1 || !first_obs || p_locs < 0 || p_locs > std::min(p, kDesignLocsMax) || (p_locs > 0 && !locs_cols))
+    return fail_msg(c, NNGP_ERR_ARG, "design_set: p >= 1, first_obs, and 0 <= p_locs <= min(p, 31) columns");
+  std::vector<int> cols(p_locs), fo(c->n);
+  std::vector<char> seen(p, 0);
+  for (int j = 0; j < p_locs; ++j) {
+    const int col = locs_cols[j];
+    if (col < 1 || col > p || seen[col - 1])
+      return fail_msg(c, NNGP_ERR_ARG, "design_set: locs_cols must be distinct columns in 1..p");
+    seen[col - 1] = 1;
+    cols[j] = col - 1;
+  }
+  for (int i = 0; i < c->n; ++i) {
+    if (first_obs[i] < 1 || first_obs[i] > c->n_obs)
+      return fail_msg(c, NNGP_ERR_ARG, "design_set: first_obs outside 1..n_obs");
+    fo[i] = first_obs[i] - 1;
+  }
+  if ((rc = set_device(c))) return rc;
+  design_free(c);
+  Design* D = new (std::nothrow) Design();
+  if (!D) return fail_msg(c, NNGP_ERR_NOMEM, "design_set: host allocation failed");
+  D->p = p;
+  D->q = p_locs + 1;
+  const int q = D->q, C = c->C;
+  const size_t n = (size_t)c->n, n_obs = (size_t)c->n_obs;
+  const int npairs = q * (q + 1) / 2;
+  D->res_stride = std::max(p + 1, q + npairs);
+  D->coef_len = (size_t)C * (2 * (size_t)(q - 1) + (size_t)p);
+  const size_t part_len = std::max((size_t)(p + 1) * reg_parts(c->n_obs), (size_t)npairs * reg_parts(c->n)) * C;
+  int *fo_d = nullptr, *cols_d = nullptr;
+  bool ok = dalloc(&D->X_d, n_obs * p) == hipSuccess && dalloc(&D->part_d, part_len) == hipSuccess &&
+            dalloc(&D->res_d, (size_t)C * D->res_stride) == hipSuccess && dalloc(&D->coef_d, D->coef_len) == hipSuccess &&
+            hipHostMalloc((void**)&D->res_h, sizeof(double) * C * D->res_stride, hipHostMallocDefault) == hipSuccess &&
+            hipHostMalloc((void**)&D->coef_h, sizeof(double) * Design::kRing * std::max<size_t>(D->coef_len, 1),
+                          hipHostMallocDefault) == hipSuccess;
+  if (ok && q > 1) {
+    ok = dalloc(&D->Xl1_d, n * q) == hipSuccess && dalloc(&D->oth_d, n * C) == hipSuccess &&
+         dalloc(&D->bo_d, n * C) == hipSuccess && dalloc(&fo_d, n) == hipSuccess && dalloc(&cols_d, (size_t)q) == hipSuccess;
+    for (int k = 0; ok && k < C; ++k) ok = dalloc(&D->sx_d[k], n * q) == hipSuccess;
+  }
+  for (int r = 0; ok && r < Design::kRing; ++r)
+    ok = hipEventCreateWithFlags(&D->coef_ev[r], hipEventDisableTiming) == hipSuccess;
+  hipError_t e = hipSuccess;
+  if (ok) {
+    // X once for all chains; Xl1 gathered from it on the device, at device rows
+    e = hipMemcpyAsync(D->X_d, X, sizeof(double) * n_obs * p, hipMemcpyHostToDevice, c->st);
+    if (e == hipSuccess && q > 1) {
+      e = hipMemcpyAsync(fo_d, fo.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->st);
+      if (e == hipSuccess) e = hipMemcpyAsync(cols_d, cols.data(), sizeof(int) * (q - 1), hipMemcpyHostToDevice, c->st);
+      if (e == hipSuccess) e = launch_design_gather(c->st, c->n, c->n_obs, q, c->dpos_d, fo_d, cols_d, D->X_d, D->Xl1_d);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);  // the host arrays are read until here
+  }
+  if (fo_d) hipFree(fo_d);
+  if (cols_d) hipFree(cols_d);
+  if (!ok || e != hipSuccess) {
+    hipGetLastError();
+    D->release();
+    delete D;
+    if (!ok) return fail_msg(c, NNGP_ERR_NOMEM, "design_set: the design does not fit (device or pinned allocation failed)");
+    return fail_hip(c, e, "design_set");
+  }
+  for (int k = 0; k < C; ++k) D->gram[k].assign((size_t)q * q, 0.0);
+  c->dsg = D;
+  return NNGP_OK;
+}
+
+// the next slot of the coefficient ring (its last copy has run)
+static int design_coef_slot(nngp_ctx* c, double** slot, int* r_out) {
+  Design* D = c->dsg;
+  const int r = D->coef_next;
+  D->coef_next = (r + 1) % Design::kRing;
+  HIPCHK(c, hipEventSynchronize(D->coef_ev[r]));
+  *slot = D->coef_h + (size_t)r * D->coef_len;
+  *r_out = r;
+  return NNGP_OK;
+}
+
+static int design_coef_upload(nngp_ctx* c, const double* slot, int r) {
+  Design* D = c->dsg;
+  if (D->coef_len) HIPCHK(c, hipMemcpyAsync(D->coef_d, slot, sizeof(double) * D->coef_len, hipMemcpyHostToDevice, c->st));
+  HIPCHK(c, hipEventRecord(D->coef_ev[r], c->st));
+  return NNGP_OK;
+}
+
+static bool design_mask_ok(const nngp_ctx* c, int chain_mask) { return chain_mask > 0 && chain_mask < (1 << c->C); }
+
+int nngp_design_mean_stats_chains(nngp_ctx* c, int chain_mask, const double* beta0, double* out) {
+  if (!c || !beta0 || !out || !design_mask_ok(c, chain_mask))
+    return fail_msg(c, NNGP_ERR_ARG, "design_mean_stats_chains: bad args");
+  { int rs_ = replica_fresh(c); if (rs_) return rs_; }
+  Design* D = c->dsg;
+  if (!D) return fail_msg(c, NNGP_ERR_STATE, "design_mean_stats_chains: no design (nngp_design_set)");
+  RegJobs J;
+  RegSlots S{};
+  for (int k = 0; k < c->C; ++k) {
+    if (!((chain_mask >> k) & 1)) continue;
+    if (!c->ch[k].have_field) return fail_msg(c, NNGP_ERR_STATE, "design_mean_stats_chains: no field");
+    J.chain[J.M] = S.slot[J.M] = k;
+    J.field[J.M] = c->ch[k].field_d;
+    J.a[J.M] = beta0[k];
+    ++J.M;
+  }
+  int rc;
+  if ((rc = set_device(c))) return rc;
+  const int nv = D->p + 1;
+  HIPCHK(c, launch_design_mean_stats(c->st, c->n_obs, D->p, c->y_d, c->lm_d, D->X_d, J, D->part_d));
+  HIPCHK(c, launch_reg_reduce(c->st, D->part_d, reg_parts(c->n_obs), J.M, nv, S, D->res_stride, 0, D->res_d));
+  HIPCHK(c, hipMemcpyAsync(D->res_h, D->res_d, sizeof(double) * c->C * D->res_stride, hipMemcpyDeviceToHost, c->st));
+  { int ss_ = sync_stream(c); if (ss_) return ss_; }
+  for (int m = 0; m < J.M; ++m)
+    std::memcpy(out + (size_t)J.chain[m] * nv, D->res_h + (size_t)J.chain[m] * D->res_stride, sizeof(double) * nv);
+  return NNGP_OK;
+}
+
+int nngp_design_interweave_stats_chains(nngp_ctx* c, int chain_mask, const double* shift, const double* beta_locs,
+                                        double* t, double* gram, int* refreshed) {
+  if (!c || !shift || !beta_locs || !t || !gram || !refreshed || !design_mask_ok(c, chain_mask))
+    return fail_msg(c, NNGP_ERR_ARG, "design_interweave_stats_chains: bad args");
+  { int rs_ = replica_fresh(c); if (rs_) return rs_; }
+  Design* D = c->dsg;
+  if (!D || D->q < 2)
+    return fail_msg(c, NNGP_ERR_STATE, "design_interweave_stats_chains: no design with interweaved columns");
+  const int q = D->q, npairs = q * (q + 1) / 2, n = c->n;
+  RegJobs J, R;  // all chains of the mask; those whose SX is behind their current factor
+  RegSlots S{}, SR{};
+  for (int k = 0; k < c->C; ++k) {
+    if (!((chain_mask >> k) & 1)) continue;
+    const ChainState& st = c->ch[k];
+    if (!st.have_factor[0] || !st.have_field)
+      return fail_msg(c, NNGP_ERR_STATE, "design_interweave_stats_chains: need the current factor and the field");
+    J.chain[J.M] = S.slot[J.M] = k;
+    J.field[J.M] = st.field_d;
+    J.linv[J.M] = st.linv_d[0];
+    J.sx[J.M] = D->sx_d[k];
+    J.a[J.M] = shift[k];
+    ++J.M;
+    if (D->sx_lgen[k] != st.lgen[0]) {
+      R.chain[R.M] = SR.slot[R.M] = k;
+      R.linv[R.M] = st.linv_d[0];
+      R.sx[R.M] = D->sx_d[k];
+      ++R.M;
+    }
+  }
+  int rc, r;
+  if ((rc = set_device(c))) return rc;
+  double* slot;
+  if ((rc = design_coef_slot(c, &slot, &r))) return rc;
+  for (int m = 0; m < J.M; ++m)
+    std::memcpy(slot + (size_t)J.chain[m] * (q - 1), beta_locs + (size_t)J.chain[m] * (q - 1), sizeof(double) * (q - 1));
+  if ((rc = design_coef_upload(c, slot, r))) return rc;
+  const int nparts = reg_parts(n);
+  if (R.M) {
+    HIPCHK(c, launch_design_sx(c->st, c->nn_d, n, c->b, q, D->Xl1_d, R));
+    HIPCHK(c, launch_design_gram(c->st, n, q, R, D->part_d));
+    HIPCHK(c, launch_reg_reduce(c->st, D->part_d, nparts, R.M, npairs, SR, D->res_stride, q, D->res_d));
+  }
+  HIPCHK(c, launch_design_other(c->st, n, q, D->Xl1_d, J, D->coef_d, D->oth_d));
+  HIPCHK(c, launch_design_spmv(c->st, c->nn_d, n, c->b, J, D->oth_d, D->bo_d));
+  HIPCHK(c, launch_design_tstats(c->st, n, q, J, D->bo_d, D->part_d));
+  HIPCHK(c, launch_reg_reduce(c->st, D->part_d, nparts, J.M, q, S, D->res_stride, 0, D->res_d));
+  HIPCHK(c, hipMemcpyAsync(D->res_h, D->res_d, sizeof(double) * c->C * D->res_stride, hipMemcpyDeviceToHost, c->st));
+  { int ss_ = sync_stream(c); if (ss_) return ss_; }
+  for (int m = 0; m < R.M; ++m) {
+    const int k = R.chain[m];
+    const double* g = D->res_h + (size_t)k * D->res_stride + q;
+    for (int a = 0, pair = 0; a < q; ++a)
+      for (int b2 = a; b2 < q; ++b2, ++pair) D->gram[k][(size_t)a * q + b2] = D->gram[k][(size_t)b2 * q + a] = g[pair];
+    D->sx_lgen[k] = c->ch[k].lgen[0];
+  }
+  for (int m = 0; m < J.M; ++m) {
+    const int k = J.chain[m];
+    std::memcpy(t + (size_t)k * q, D->res_h + (size_t)k * D->res_stride, sizeof(double) * q);
+    std::memcpy(gram + (size_t)k * q * q, D->gram[k].data(), sizeof(double) * q * q);
+    refreshed[k] = 0;
+  }
+  for (int m = 0; m < R.M; ++m) refreshed[R.chain[m]] = 1;
+  return NNGP_OK;
+}
+
+int nngp_design_commit_chains(nngp_ctx* c, int chain_mask, const double* shift, const double* beta_locs_old,
+                              const double* beta_locs_new, const double* beta0, const double* beta) {
+  if (!c || !shift || !beta0 || !beta || !design_mask_ok(c, chain_mask))
+    return fail_msg(c, NNGP_ERR_ARG, "design_commit_chains: bad args");
+  Design* D = c->dsg;
+  if (D && D->q > 1 && (!beta_locs_old || !beta_locs_new))
+    return fail_msg(c, NNGP_ERR_ARG, "design_commit_chains: beta_locs_old and beta_locs_new are needed with p_locs > 0");
+  { int rs_ = replica_fresh(c); if (rs_) return rs_; }
+  if (!D) return fail_msg(c, NNGP_ERR_STATE, "design_commit_chains: no design (nngp_design_set)");
+  const int q = D->q, p = D->p;
+  RegJobs J;
+  for (int k = 0; k < c->C; ++k) {
+    if (!((chain_mask >> k) & 1)) continue;
+    if (!c->ch[k].have_field) return fail_msg(c, NNGP_ERR_STATE, "design_commit_chains: no field");
+    J.chain[J.M] = k;
+    J.field[J.M] = c->ch[k].field_d;
+    J.mu[J.M] = c->ch[k].mu_d;
+    J.a[J.M] = shift[k];
+    J.b[J.M] = beta0[k];
+    ++J.M;
+  }
+  int rc, r;
+  if ((rc = set_device(c))) return rc;
+  double* slot;
+  if ((rc = design_coef_slot(c, &slot, &r))) return rc;
+  const size_t ql = (size_t)(q - 1), o_new = (size_t)c->C * ql, o_beta = 2 * o_new;
+  for (int m = 0; m < J.M; ++m) {
+    const int k = J.chain[m];
+    if (ql) {
+      std::memcpy(slot + k * ql, beta_locs_old + k * ql, sizeof(double) * ql);
+      std::memcpy(slot + o_new + k * ql, beta_locs_new + k * ql, sizeof(double) * ql);
+    }
+    std::memcpy(slot + o_beta + (size_t)k * p, beta + (size_t)k * p, sizeof(double) * p);
+  }
+  if ((rc = design_coef_upload(c, slot, r))) return rc;
+  HIPCHK(c, launch_design_field(c->st, c->n, q, D->Xl1_d, J, D->coef_d, D->coef_d + o_new));
+  HIPCHK(c, launch_design_mu(c->st, c->n_obs, p, D->X_d, J, D->coef_d + o_beta));
+  // the state nngp_set_field + nngp_set_mu(mu, beta0) leave (stream-ordered: no host sync)
+  for (int m = 0; m < J.M; ++m) {
+    const int k = J.chain[m];
+    ChainState& st = c->ch[k];
+    c->stale_mask &= ~(1 << k);
+    st.fgen = ++c->gen;
+    st.mu_is_const = false;
+    st.mu_beta0 = beta0[k];
+    st.res_stale = true;
+    st.have_mu = true;
+  }
+  return NNGP_OK;
+}
+
+int nngp_get_mu(nngp_ctx* c, double* mu) {
+  if (!c || !mu) return NNGP_ERR_ARG;
+  ChainState& S = c->ch[c->cur];
+  if (!S.have_mu) return fail_msg(c, NNGP_ERR_STATE, "get_mu: no mu");
+  int rc;
+  if ((rc = set_device(c))) return rc;
+  { int ss_ = sync_stream(c); if (ss_) return ss_; }
+  if (S.mu_is_const) {
+    std::fill(mu, mu + c->n_obs, S.mu_beta0);
+    return NNGP_OK;
+  }
+  HIPCHK(c, hipMemcpy(mu, S.mu_d, sizeof(double) * c->n_obs, hipMemcpyDeviceToHost));
   return NNGP_OK;
 }
 

@@ -21,6 +21,18 @@ sum_squared_residuals :281             ctx.sum_squared_residuals
 sparse_chol %*% X :79,82,147,241       ctx.spmv
 =====================================  =====================================
 
+regression="device" keeps the design matrix in the context and replaces the
+host arithmetic of the regression block (:77-83,145-151,226-250) by three
+batched device calls; the small dense solves, Choleskys and the normal draws
+stay here, in the host path's order:
+
+=====================================  =====================================
+crossprod(y - field + beta_0, X1) :230 ctx.design_mean_stats_chains
+crossprod(B other, B Xl1), B Xl1 :79,  ctx.design_interweave_stats_chains
+  :147,:240-241
+field and mu updates :233,240,245,249  ctx.design_commit_chains
+=====================================  =====================================
+
 Chains live in device contexts (up to 4 chains per context, contexts possibly
 on distinct devices) instead of forked ``mclapply`` workers: HIP must never
 be initialised before a fork.  Each chain's iteration is a generator that
@@ -42,7 +54,7 @@ import threading
 
 import numpy as np
 
-from ._lib import NNGP_ERR_CHOL, NNGPError
+from ._lib import NNGP_ERR_CHOL, NNGP_ERR_STATE, NNGPError
 from .context import ChainContext, make_chain_views
 from .model import covparms
 
@@ -64,6 +76,26 @@ def _interweave_prep(ctx, X, va):
     prec = SX.T @ SX
     cov = np.linalg.inv(prec)
     return {"Xl": Xl, "SX": SX, "covmat": cov, "covmat_chol": np.linalg.cholesky(cov).T}
+
+
+_DESIGN_METHODS = ("design_set", "design_mean_stats_chains", "design_interweave_stats_chains",
+                   "design_commit_chains")
+
+
+def _design_ensure(ctx, X, va):
+    """regression="device": the design of X resident in the context of `ctx`,
+    uploaded once per context (the chains of a context share it, and a later
+    update call with the same X finds it there).  Raises when the context
+    cannot hold it: no entry points, a shard context, or no memory."""
+    owner = getattr(ctx, "ctx", None) or ctx
+    if not all(hasattr(owner, m) for m in _DESIGN_METHODS):
+        raise NNGPError(NNGP_ERR_STATE, "regression='device': this context has no design entry points")
+    held = getattr(owner, "_design_held", None)
+    locs = tuple(int(j) for j in X["locs"])
+    if held is not None and held[0] is X["X"] and held[1] == locs:
+        return
+    owner.design_set(X["X"], va["hctam_scol_1"], locs)
+    owner._design_held = (X["X"], locs)
 
 
 def _prefault(arr: np.ndarray) -> threading.Thread:
@@ -96,7 +128,8 @@ def _proposal_ok(status, on_chol_error):
 
 
 def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_iterations_update,
-                   field_thinning, ancillary, n_chromatic, iter_start, seed, on_chol_error="error", var_y=None):
+                   field_thinning, ancillary, n_chromatic, iter_start, seed, on_chol_error="error", var_y=None,
+                   regression="host"):
     """Chain i's n_iterations_update Gibbs iterations; yields its device
     requests and receives their results, so that the chains of one context
     are served by one batched call per step (one host sync for all of them):
@@ -106,10 +139,16 @@ def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_ite
           -> (status, (loglik(1), loglik(0))) | None when covparms is None
       ("sweep", n_sweeps, beta_0, log_scale, lnv, key, counter) -> None
       ("ssr", beta_0)                          -> sum of squared residuals
+    and, with regression="device" and covariates,
+      ("dmean", beta_0)                        -> crossprod(y - field + beta_0, cbind(1, X))
+      ("dinter", shift, beta_locs)             -> (t, Gram matrix, refreshed)
+      ("dcommit", shift, beta_locs_old | None, beta_locs_new | None, beta_0, beta) -> None
     Every chain yields every step of an iteration (None = nothing to do), so
     the chains stay in lockstep.  Returns {"state", "records", "acceptance"}."""
     # (runif(1) is rng.random(): the same draw as rng.uniform() bit for bit,
     # without its argument handling -- 0.36 vs 1.5 us a call)
+    if regression not in ("host", "device"):
+        raise ValueError("regression must be 'host' or 'device'")
     rng = np.random.default_rng(int(iter_start) + i + 1)
     key = _philox_key(iter_start, i + 1, seed)
     covfun = space_time_model["covfun"]["stationary_covfun"]
@@ -122,6 +161,9 @@ def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_ite
     has_X = X.get("X") is not None
     has_locs = has_X and len(X["locs"]) > 0
     n_shape = len(sp_names)
+    dev_reg = regression == "device" and has_X
+    if dev_reg:
+        _design_ensure(ctx, X, va)
 
     rec = {"beta_0": np.zeros((n_iterations_update, 1)),
            "log_scale": np.zeros((n_iterations_update, 1)),
@@ -158,7 +200,7 @@ def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_ite
     # Vecchia factor of the current state (:67-74)
     ctx.factor(0, covfun, covparms(sp_names, params["shape"]))
     ctx.set_field(params["field"])
-    iw = _interweave_prep(ctx, X, va) if has_locs else None
+    iw = _interweave_prep(ctx, X, va) if has_locs and not dev_reg else None
 
     def mu_of():
         if has_X:
@@ -186,7 +228,7 @@ def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_ite
                     ctx.accept_field()
                     ctx.accept_factor()
                     acc_anc[it - 1] = 1
-                    if has_locs:
+                    if has_locs and not dev_reg:
                         iw = _interweave_prep(ctx, X, va)
             if adapt and it % 25 == 0:
                 a = acc_anc[it - 25:it].mean()
@@ -214,7 +256,7 @@ def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_ite
                 params["log_scale"] = new_ls
                 ctx.accept_factor()
                 acc_suf[it - 1] = 1
-                if has_locs:
+                if has_locs and not dev_reg:
                     iw = _interweave_prep(ctx, X, va)
         if adapt and it % 25 == 0:
             a = acc_suf[it - 25:it].mean()
@@ -229,7 +271,31 @@ def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_ite
             beta_covmat = math.exp(params["log_scale"]) / oqo
             beta_mean = math.exp(-params["log_scale"]) * oqf * beta_covmat
             params["beta_0"] = float(beta_mean + math.sqrt(beta_covmat) * rng.normal())
-        if has_X:
+        if dev_reg:
+            # the host path's draws, in its order, on statistics from the device
+            b0_old = params["beta_0"]
+            stats = yield ("dmean", b0_old)
+            beta_mean = stats @ X["solve_1XT1X"]
+            innov = beta_mean + math.exp(0.5 * params["log_noise_variance"]) * (
+                X["chol_solve_1XT1X"].T @ rng.normal(size=len(stats)))
+            shift = float(innov[0]) - b0_old
+            params["beta_0"] = float(innov[0])
+            params["beta"] = innov[1:].copy()
+            bl_old = bl_new = None
+            if has_locs:
+                locs_cols = X["locs"]
+                bl_old = params["beta"][locs_cols].copy()
+                t, gram, refreshed = yield ("dinter", shift, bl_old)
+                if refreshed or iw is None:  # B Xl1 was formed again: the current factor changed
+                    cov = np.linalg.inv(gram)
+                    iw = {"covmat": cov, "covmat_chol": np.linalg.cholesky(cov).T}
+                bm = iw["covmat"] @ t
+                innov = bm + math.exp(0.5 * params["log_scale"]) * (iw["covmat_chol"].T @ rng.normal(size=len(locs_cols) + 1))
+                params["beta_0"] = float(innov[0])
+                params["beta"][locs_cols] = innov[1:]
+                bl_new = innov[1:].copy()
+            yield ("dcommit", shift, bl_old, bl_new, params["beta_0"], params["beta"].copy())
+        elif has_X:
             field = ctx.get_field()
             X1 = np.column_stack([np.ones(n_obs), X["X"]])
             resid = observed_field - field[va["locs_match"] - 1] + params["beta_0"]
@@ -249,7 +315,8 @@ def _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_ite
                 params["beta"][locs_cols] = innov[1:]
                 field = other - iw["Xl"] @ params["beta"][locs_cols]
             ctx.set_field(field)
-        ctx.set_mu(mu_of(), params["beta_0"])
+        if not dev_reg:
+            ctx.set_mu(mu_of(), params["beta_0"])
 
         # ---- chromatic sampling of the field (:257-275)
         yield ("sweep", n_chromatic, params["beta_0"], params["log_scale"], params["log_noise_variance"],
@@ -332,15 +399,55 @@ def _serve_one(ctx, req):
         return int(st[k]), (float(lp[k]), float(lc[k]))
     if kind == "ssr":
         return ctx.sum_squared_residuals(req[1])
+    if kind in ("dmean", "dinter", "dcommit"):
+        owner = getattr(ctx, "ctx", None)
+        k = ctx.chain if owner is not None else 0
+        out = {}
+        _serve_design(owner or ctx, kind, {0: k}, {0: req}, out)
+        return out[0]
     ctx.sweep(*req[1:])
     return None
 
 
+def _serve_design(owner, kind, chain_of, reqs, out):
+    """The regression requests `reqs` (id -> request, all of `kind`) of the
+    chains chain_of[id] of one context in one batched call; results into out."""
+    K = getattr(owner, "n_chains", 1)
+    mask = 0
+    for i in reqs:
+        mask |= 1 << chain_of[i]
+
+    def rows(col, width):
+        a = np.zeros((K, width))
+        for i, r in reqs.items():
+            if r[col] is not None:
+                a[chain_of[i]] = r[col]
+        return a
+
+    def vec(col):
+        return rows(col, 1)[:, 0]
+
+    first = next(iter(reqs.values()))
+    if kind == "dmean":
+        res = owner.design_mean_stats_chains(mask, vec(1))
+        out.update({i: np.array(res[chain_of[i]]) for i in reqs})
+    elif kind == "dinter":
+        t, gram, refreshed = owner.design_interweave_stats_chains(mask, vec(1), rows(2, len(first[2])))
+        out.update({i: (np.array(t[chain_of[i]]), np.array(gram[chain_of[i]]), int(refreshed[chain_of[i]]))
+                    for i in reqs})
+    else:
+        ql = 0 if first[2] is None else len(first[2])
+        owner.design_commit_chains(mask, vec(1), rows(2, ql) if ql else None, rows(3, ql) if ql else None,
+                                   vec(4), rows(5, len(first[5])))
+        out.update({i: None for i in reqs})
+
+
 def _run_chain(i, state, ctx, X, observed_field, space_time_model, va, n_iterations_update,
-               field_thinning, ancillary, n_chromatic, iter_start, seed, on_chol_error="error"):
+               field_thinning, ancillary, n_chromatic, iter_start, seed, on_chol_error="error", regression="host"):
     """One chain alone (each request served on its own)."""
     prog = _chain_program(i, state, ctx, X, observed_field, space_time_model, va, n_iterations_update,
-                          field_thinning, ancillary, n_chromatic, iter_start, seed, on_chol_error)
+                          field_thinning, ancillary, n_chromatic, iter_start, seed, on_chol_error,
+                          regression=regression)
     try:
         req = next(prog)
         while True:
@@ -396,6 +503,9 @@ def _serve_group(owner, ids, reqs, contexts, out):
         r = owner.sum_squared_residuals_chains(mask, b0)
         out.update({i: float(r[contexts[i].chain]) for i in ids})
         return True
+    if kind in ("dmean", "dinter", "dcommit"):
+        _serve_design(owner, kind, {i: contexts[i].chain for i in ids}, {i: reqs[i] for i in ids}, out)
+        return True
     if len(ids) != k or len({reqs[i][1] for i in ids}) != 1:
         return False
     order = sorted(ids, key=lambda i: contexts[i].chain)
@@ -439,12 +549,18 @@ def _drive(programs, contexts):
 def mcmc_nngp_update_Gaussian(locs, X, observed_field, space_time_model, vecchia_approx, states,
                               n_iterations_update, n_cores=None, field_thinning=1.0, ancillary=True,
                               n_chromatic=10, iterations=None, contexts=None, seed=1, devices=None,
-                              on_chol_error="error"):
+                              on_chol_error="error", regression="host"):
     """Returns one {"state", "records"} per chain (update_Gaussian.R:315).
     on_chol_error: "error" (GpGp's behaviour: a non positive definite local
-    covariance of a proposal raises) or "reject" (the proposal is rejected)."""
+    covariance of a proposal raises) or "reject" (the proposal is rejected).
+    regression: "host" (the regression block's array arithmetic in numpy) or
+    "device" (the design matrix resident in the chains' contexts, the block's
+    array operations as batched device calls; raises when a context cannot hold
+    the design -- there is no fallback to the host path)."""
     if on_chol_error not in ("error", "reject"):
         raise ValueError("on_chol_error must be 'error' or 'reject'")
+    if regression not in ("host", "device"):
+        raise ValueError("regression must be 'host' or 'device'")
     iter_start = int(iterations[-1, 0]) if iterations is not None else 0
     names = list(states.keys()) if isinstance(states, dict) else [f"chain_{i + 1}" for i in range(len(states))]
     st_list = list(states.values()) if isinstance(states, dict) else list(states)
@@ -455,6 +571,6 @@ def mcmc_nngp_update_Gaussian(locs, X, observed_field, space_time_model, vecchia
     var_y = float(np.var(y, ddof=1))  # var(observed_field), :167,286 (once for all chains)
     programs = [_chain_program(i, st, contexts[i], X, y, space_time_model, vecchia_approx,
                                int(n_iterations_update), float(field_thinning), bool(ancillary),
-                               int(n_chromatic), iter_start, seed, on_chol_error, var_y)
+                               int(n_chromatic), iter_start, seed, on_chol_error, var_y, regression)
                 for i, st in enumerate(st_list)]
     return dict(zip(names, _drive(programs, contexts)))

@@ -42,6 +42,13 @@
  *                              estimate.R:88-94; predicted_field_summary, predict.R:57-58)
  *   nngp_predict_field ....... the per-sample body of mcmc_nngp_predict_field,
  *                              Scripts/mcmc_nngp_predict.R:39-53, for all samples of a chain
+ *   nngp_design_set .......... X, X$locs and beta_interweaved_* kept for the call,
+ *                              Scripts/mcmc_nngp_update_Gaussian.R:77-83,145-151
+ *   nngp_design_mean_stats_chains      crossprod(y - field[locs_match] + beta_0, cbind(1, X)),
+ *                              update_Gaussian.R:230
+ *   nngp_design_interweave_stats_chains  crossprod(sparse_chol %*% other, sparse_chol_X) and
+ *                              beta_interweaved_precision, update_Gaussian.R:79,240-241
+ *   nngp_design_commit_chains  the field and mu updates, update_Gaussian.R:233,240,245,249
  *   nngp_spmv / nngp_tri_solve sparse_chol %*% X (update_Gaussian.R:79,147) /
  *                              Matrix::solve (initialize.R:208, predict.R:46)
  */
@@ -55,7 +62,7 @@
 extern "C" {
 #endif
 
-#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats, nngp_predict_field, nngp_predict_stats: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
+#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
 #define NNGP_SHARD_ID_BYTES 128 /* RCCL unique id */
 #define NNGP_IPC_HANDLE_BYTES 192 /* HIP IPC handles of a tile shard's granule buffer, w replica, flags */
 
@@ -280,6 +287,55 @@ int nngp_tri_solve(nngp_ctx* ctx, int which, const double* u, double* x);
  * ticket order of the rescue; forced ticket orders (NNGP_TRI_RESCUE=1) do not
  * count.  Waits for the context's stream. */
 int nngp_tri_rescues(nngp_ctx* ctx, long long* out);
+
+/* ---------- regression coefficients (update_Gaussian.R:77-83,145-151,226-250) ----------
+ * The design matrix resident in the context and the three array operations
+ * of the regression block, batched over the chains in chain_mask (bit k =
+ * chain k; per-chain arrays have n_chains rows, rows of other chains are
+ * neither read nor written).  The small dense algebra -- the (p+1) and
+ * (p_locs+1) square solves, Choleskys and the normal draws -- stays with the
+ * caller.  Chain k's results are bitwise the same whatever other chains are in
+ * the mask and from run to run (fixed reduction trees, no floating-point
+ * atomics).  The entries that read the field refuse a tile-shard replica that
+ * is behind (nngp_shard_sync), like the other readers.
+ *
+ * nngp_design_set uploads X (n_obs x p column-major, centred by the caller)
+ * once for all chains and builds Xl1 = cbind(1, X[first_obs, locs_cols]),
+ * n x (p_locs+1), on the device.  first_obs: length n, 1-based, the first
+ * observation of each location (hctam_scol_1); locs_cols: p_locs distinct
+ * 1-based columns of X (X$locs), p_locs may be 0.  X == NULL frees the design.
+ * NNGP_ERR_ARG (checked before any HIP call): p < 1, p_locs outside
+ * 0..min(p, 31), a column out of range or repeated, a first_obs entry outside
+ * 1..n_obs.  NNGP_ERR_NOMEM: the design does not fit (no design is left).
+ * NNGP_ERR_STATE: a shard context. */
+int nngp_design_set(nngp_ctx* ctx, const double* X, int p, const int* first_obs, const int* locs_cols,
+                    int p_locs);
+/* out (n_chains x (p+1), row k = chain k) = crossprod(y - field_k[locs_match]
+ * + beta0[k], cbind(1, X)) (update_Gaussian.R:230).  X is read once for all
+ * chains of the mask; one host sync. */
+int nngp_design_mean_stats_chains(nngp_ctx* ctx, int chain_mask, const double* beta0, double* out);
+/* Per chain: other = field + shift[k] + Xl beta_locs[k,] (Xl = Xl1 without its
+ * first column; beta_locs n_chains x p_locs), t[k,] = crossprod(B_cur other,
+ * SX_k) (t: n_chains x (p_locs+1)), SX_k = B_cur Xl1 (update_Gaussian.R:240-241).
+ * SX_k stays on the device and is formed again inside this call when chain
+ * k's current factor changed since (all columns in one pass over the rows);
+ * refreshed[k] = 1 then, else 0.  gram[k,,] = crossprod(SX_k)
+ * (beta_interweaved_precision, :79; n_chains x (p_locs+1) x (p_locs+1)) is
+ * always returned, from the call that formed SX_k when refreshed[k] = 0.
+ * The field is not modified.  One host sync.  NNGP_ERR_STATE: p_locs == 0, no
+ * design, factor or field. */
+int nngp_design_interweave_stats_chains(nngp_ctx* ctx, int chain_mask, const double* shift,
+                                        const double* beta_locs, double* t, double* gram, int* refreshed);
+/* field_k = (field_k + shift[k] + Xl beta_locs_old[k,]) - Xl beta_locs_new[k,]
+ * (update_Gaussian.R:233,240,245; column sums in column order; the two
+ * beta_locs may be NULL when p_locs == 0: the shift alone) and mu_k = beta0[k]
+ * + X beta[k,] (beta n_chains x p; :249) on the device.  Stream-ordered, no
+ * host sync.  Leaves the context as nngp_set_field(new field) followed by
+ * nngp_set_mu(mu, beta0[k]) would. */
+int nngp_design_commit_chains(nngp_ctx* ctx, int chain_mask, const double* shift, const double* beta_locs_old,
+                              const double* beta_locs_new, const double* beta0, const double* beta);
+/* the selected chain's current mu (n_obs doubles); test hook like nngp_get_sweep_r */
+int nngp_get_mu(nngp_ctx* ctx, double* mu);
 
 /* ---------- colour-sharded sweep (multi-GPU) ----------
  * The chromatic sweep of ONE set of chains split over n_ranks contexts (one

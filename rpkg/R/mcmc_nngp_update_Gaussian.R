@@ -13,6 +13,10 @@
 #   chromatic sampling (:257-275)                          -> nngp_sweep_chains (Philox normals on the device)
 #   SSR (:281)                                             -> nngp_sum_squared_residuals_chains
 #   sparse_chol %*% X (:79,82,147,241)                     -> nngp_spmv
+#   regression = "device": the regression block's arrays (:77-83,145-151,226-250) stay on the
+#     device -- nngp_design_set once, then per iteration nngp_design_mean_stats_chains,
+#     nngp_design_interweave_stats_chains and nngp_design_commit_chains for all chains at once;
+#     the small solves, chol() and the rnorm() draws stay here, in the same order per chain
 #   records$field (:305-311)                               -> nngp_record_field / nngp_get_records
 # parallel::mclapply over chains (:25-26) is replaced by ONE device context
 # holding the chains (HIP must not be initialised before a fork()), advanced in
@@ -44,8 +48,10 @@
 mcmc_nngp_update_Gaussian <- function(locs, X, observed_field, space_time_model, vecchia_approx, states,
                                       n_iterations_update, n_cores = NULL, field_thinning = 1,
                                       ancillary = TRUE, n_chromatic = 10, iterations = NULL,
-                                      contexts = NULL, device = -1L, on_chol_error = c("error", "reject")) {
+                                      contexts = NULL, device = -1L, on_chol_error = c("error", "reject"),
+                                      regression = c("host", "device")) {
   on_chol_error <- match.arg(on_chol_error)
+  regression <- match.arg(regression)
   iter_start <- if (is.null(iterations)) 0 else iterations[nrow(iterations), 1]
   C <- length(states)
   if (C > 4) stop("nngp: at most 4 chains per device context")
@@ -60,6 +66,9 @@ mcmc_nngp_update_Gaussian <- function(locs, X, observed_field, space_time_model,
   var_y <- var(observed_field)
   has_X <- !is.null(X$X)
   has_locs <- has_X && length(X$locs) > 0
+  # regression = "device": no fallback -- nngp_design_set stops when the context cannot hold X
+  dev_reg <- regression == "device" && has_X
+  if (dev_reg) nngp_design_set(ctx, X$X, vecchia_approx$hctam_scol_1, X$locs)
   n_saved <- round(n_iterations_update * field_thinning)
   all_chains <- .nngp_mask(seq_len(C))
   adapt <- iter_start >= 0 && iter_start <= 2000
@@ -126,7 +135,7 @@ mcmc_nngp_update_Gaussian <- function(locs, X, observed_field, space_time_model,
     }
     nngp_factor(ctx, 0L, covfun, nngp_covparms(sp, P[[i]]$shape))
     nngp_set_field(ctx, P[[i]]$field)
-    if (has_locs) IW[[i]] <- .nngp_interweave(ctx, X, vecchia_approx)
+    if (has_locs && !dev_reg) IW[[i]] <- .nngp_interweave(ctx, X, vecchia_approx)
     set_mu(i)
   }
   cp_rows <- function(shapes, idx) {
@@ -195,7 +204,7 @@ mcmc_nngp_update_Gaussian <- function(locs, X, observed_field, space_time_model,
         nngp_set_chain(ctx, i - 1L)
         nngp_accept_factor(ctx)
         acc_suf[it, i] <- 1
-        if (has_locs) IW[[i]] <- .nngp_interweave(ctx, X, vecchia_approx)
+        if (has_locs && !dev_reg) IW[[i]] <- .nngp_interweave(ctx, X, vecchia_approx)
       }
       if (adapt && it %% 25 == 0) {
         a <- mean(acc_suf[(it - 24):it, i])
@@ -212,7 +221,7 @@ mcmc_nngp_update_Gaussian <- function(locs, X, observed_field, space_time_model,
         beta_mean <- exp(-P[[i]]$log_scale) * st0[2] * beta_cov
         P[[i]]$beta_0 <- beta_mean + sqrt(beta_cov) * draw(i, function() rnorm(1))
       }
-      if (has_X) {  # :226-247
+      if (has_X && !dev_reg) {  # :226-247
         field <- nngp_get_field(ctx)
         X1 <- cbind(1, X$X)
         resid <- observed_field - field[vecchia_approx$locs_match] + P[[i]]$beta_0
@@ -235,7 +244,42 @@ mcmc_nngp_update_Gaussian <- function(locs, X, observed_field, space_time_model,
         }
         nngp_set_field(ctx, field)
       }
-      set_mu(i)
+      if (!dev_reg) set_mu(i)
+    }
+    if (dev_reg) {  # :226-250 for every chain: statistics from the device, draws here, one commit
+      p_X <- ncol(X$X)
+      b0_old <- vec("beta_0")
+      ms <- nngp_design_mean_stats_chains(ctx, all_chains, b0_old, p_X)
+      shift <- numeric(C)
+      for (i in seq_len(C)) {
+        z <- draw(i, function() rnorm(p_X + 1))
+        innov <- as.vector(ms[, i] %*% X$solve_1XT1X + exp(.5 * P[[i]]$log_noise_variance) * t(X$chol_solve_1XT1X) %*% z)
+        shift[i] <- innov[1] - b0_old[i]
+        P[[i]]$beta_0 <- innov[1]
+        P[[i]]$beta <- innov[-1]
+      }
+      bl_old <- bl_new <- NULL
+      if (has_locs) {
+        q <- length(X$locs) + 1
+        locs_of <- function() matrix(vapply(P, function(p) p$beta[X$locs], numeric(q - 1)), q - 1, C)
+        bl_old <- locs_of()
+        iws <- nngp_design_interweave_stats_chains(ctx, all_chains, shift, bl_old)
+        for (i in seq_len(C)) {
+          if (iws$refreshed[i] == 1L || is.null(IW[[i]])) {  # B Xl1 was formed again: new current factor
+            prec <- matrix(iws$gram[, i], q, q)
+            cov_mat <- solve(prec, tol = min(rcond(prec), .Machine$double.eps))
+            IW[[i]] <- list(covmat = cov_mat, covmat_chol = chol(cov_mat))
+          }
+          bm <- IW[[i]]$covmat %*% iws$t[, i]
+          z <- draw(i, function() rnorm(q))
+          innov <- as.vector(bm + exp(.5 * P[[i]]$log_scale) * t(IW[[i]]$covmat_chol) %*% z)
+          P[[i]]$beta_0 <- innov[1]
+          P[[i]]$beta[X$locs] <- innov[-1]
+        }
+        bl_new <- locs_of()
+      }
+      nngp_design_commit_chains(ctx, all_chains, shift, bl_old, bl_new, vec("beta_0"),
+                                matrix(vapply(P, function(p) p$beta, numeric(p_X)), p_X, C))
     }
     # ---- chromatic sampling of every chain's field, one call (:257-275)
     nngp_sweep_chains(ctx, n_chromatic, vec("beta_0"), vec("log_scale"), vec("log_noise_variance"),

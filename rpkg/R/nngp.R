@@ -147,6 +147,25 @@ nngp_field_response_ratio_chains <- function(ctx, chain_mask, beta_0, log_noise_
         as.double(log_noise_variance))
 nngp_sum_squared_residuals_chains <- function(ctx, chain_mask, beta_0)
   .Call(C_nngp_sum_squared_residuals_chains, ctx, as.integer(chain_mask), as.double(beta_0))
+# Regression block on the device (update_Gaussian.R:77-83,145-151,226-250).  Per-chain matrices
+# have one column per chain.  nngp_design_set: X (n_obs x p, centred), first_obs =
+# vecchia_approx$hctam_scol_1, locs_cols = X$locs (1-based); X = NULL frees the design.
+nngp_design_set <- function(ctx, X, first_obs = NULL, locs_cols = integer(0))
+  invisible(.Call(C_nngp_design_set, ctx, if (is.null(X)) NULL else as.matrix(X) + 0, as.integer(first_obs),
+                  as.integer(locs_cols)))
+# (p+1) x n_chains: crossprod(cbind(1, X), y - field[locs_match] + beta_0) per chain
+nngp_design_mean_stats_chains <- function(ctx, chain_mask, beta_0, ncol_X)
+  .Call(C_nngp_design_mean_stats_chains, ctx, as.integer(chain_mask), as.double(beta_0), as.integer(ncol_X))
+# list(t = (p_locs+1) x n_chains, gram = (p_locs+1)^2 x n_chains, refreshed); beta_locs: p_locs x n_chains
+nngp_design_interweave_stats_chains <- function(ctx, chain_mask, shift, beta_locs)
+  .Call(C_nngp_design_interweave_stats_chains, ctx, as.integer(chain_mask), as.double(shift), as.matrix(beta_locs) + 0)
+# field and mu updates of the chains in the mask (no host sync); beta: ncol(X) x n_chains
+nngp_design_commit_chains <- function(ctx, chain_mask, shift, beta_locs_old, beta_locs_new, beta_0, beta)
+  invisible(.Call(C_nngp_design_commit_chains, ctx, as.integer(chain_mask), as.double(shift),
+                  if (is.null(beta_locs_old)) NULL else as.matrix(beta_locs_old) + 0,
+                  if (is.null(beta_locs_new)) NULL else as.matrix(beta_locs_new) + 0, as.double(beta_0),
+                  as.matrix(beta) + 0))
+nngp_get_mu <- function(ctx) .Call(C_nngp_get_mu, ctx)
 nngp_shard_ipc_handle <- function(ctx) .Call(C_nngp_shard_ipc_handle, ctx)
 nngp_shard_ipc_open <- function(ctx, handles) invisible(.Call(C_nngp_shard_ipc_open, ctx, handles))
 # collective over the ranks of a tile shard: full exchange of the replicas

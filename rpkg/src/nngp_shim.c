@@ -722,6 +722,94 @@ SEXP C_nngp_sum_squared_residuals_chains(SEXP p, SEXP mask, SEXP beta0) {
   return out;
 }
 
+/* ---------- regression block (nngp_design_*) ----------
+ * Per-chain matrix arguments and results have one COLUMN per chain: a
+ * column-major width x n_chains R matrix is the ABI's n_chains x width rows. */
+static const double* chain_cols(SEXP x, int width, int k, const char* what) {
+  if (TYPEOF(x) != REALSXP || XLENGTH(x) != (R_xlen_t)width * k)
+    Rf_error("nngp: %s must be a double matrix of %d rows with one column per chain (%d)", what, width, k);
+  return REAL(x);
+}
+
+SEXP C_nngp_design_set(SEXP p, SEXP X, SEXP first_obs, SEXP locs_cols) {
+  nngp_ctx* c = get_ctx(p);
+  if (TYPEOF(X) == NILSXP) {
+    check(nngp_design_set(c, NULL, 0, NULL, NULL, 0), c);
+    return R_NilValue;
+  }
+  nngp_info inf;
+  check(nngp_ctx_info(c, &inf), c);
+  if (TYPEOF(X) != REALSXP || !Rf_isMatrix(X) || Rf_nrows(X) != inf.n_obs)
+    Rf_error("nngp: X must be a double matrix with one row per observation (%d)", inf.n_obs);
+  if (TYPEOF(first_obs) != INTSXP || XLENGTH(first_obs) != inf.n || TYPEOF(locs_cols) != INTSXP)
+    Rf_error("nngp: first_obs must be an integer vector with one entry per location (%d), locs_cols integer", inf.n);
+  const int pl = (int)XLENGTH(locs_cols);
+  check(nngp_design_set(c, REAL(X), Rf_ncols(X), INTEGER(first_obs), pl ? INTEGER(locs_cols) : NULL, pl), c);
+  return R_NilValue;
+}
+
+SEXP C_nngp_design_mean_stats_chains(SEXP p, SEXP mask, SEXP beta0, SEXP ncol_X) {
+  nngp_ctx* c = get_ctx(p);
+  const int k = ctx_chains(c), nv = as_int(ncol_X) + 1;
+  const double* b0 = per_chain(beta0, k, "beta0");
+  if (nv < 2) Rf_error("nngp: ncol(X) >= 1");
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, nv, k));
+  memset(REAL(out), 0, sizeof(double) * (size_t)nv * k);
+  const int rc = nngp_design_mean_stats_chains(c, as_int(mask), b0, REAL(out));
+  UNPROTECT(1);
+  check(rc, c);
+  return out;
+}
+
+SEXP C_nngp_design_interweave_stats_chains(SEXP p, SEXP mask, SEXP shift, SEXP beta_locs) {
+  nngp_ctx* c = get_ctx(p);
+  const int k = ctx_chains(c);
+  if (!Rf_isMatrix(beta_locs) || Rf_nrows(beta_locs) < 1) Rf_error("nngp: beta_locs must be a p_locs x n_chains matrix");
+  const int q = Rf_nrows(beta_locs) + 1;
+  const double *sh = per_chain(shift, k, "shift"), *bl = chain_cols(beta_locs, q - 1, k, "beta_locs");
+  SEXP t = PROTECT(Rf_allocMatrix(REALSXP, q, k));
+  SEXP gram = PROTECT(Rf_allocMatrix(REALSXP, q * q, k));
+  SEXP refreshed = PROTECT(Rf_allocVector(INTSXP, k));
+  memset(REAL(t), 0, sizeof(double) * (size_t)q * k);
+  memset(REAL(gram), 0, sizeof(double) * (size_t)q * q * k);
+  for (int i = 0; i < k; ++i) INTEGER(refreshed)[i] = 0;
+  const int rc = nngp_design_interweave_stats_chains(c, as_int(mask), sh, bl, REAL(t), REAL(gram), INTEGER(refreshed));
+  if (rc) {
+    UNPROTECT(3);
+    check(rc, c);
+  }
+  SEXP v[3] = {t, gram, refreshed};
+  const char* nm[3] = {"t", "gram", "refreshed"};
+  SEXP out = named_list(3, v, nm);
+  UNPROTECT(3);
+  return out;
+}
+
+SEXP C_nngp_design_commit_chains(SEXP p, SEXP mask, SEXP shift, SEXP beta_locs_old, SEXP beta_locs_new, SEXP beta0,
+                                 SEXP beta) {
+  nngp_ctx* c = get_ctx(p);
+  const int k = ctx_chains(c);
+  if (!Rf_isMatrix(beta)) Rf_error("nngp: beta must be a ncol(X) x n_chains matrix");
+  const int pl = TYPEOF(beta_locs_old) == NILSXP ? 0 : Rf_nrows(beta_locs_old);
+  const double *sh = per_chain(shift, k, "shift"), *b0 = per_chain(beta0, k, "beta0");
+  const double* bo = pl ? chain_cols(beta_locs_old, pl, k, "beta_locs_old") : NULL;
+  const double* bn = pl ? chain_cols(beta_locs_new, pl, k, "beta_locs_new") : NULL;
+  const double* b = chain_cols(beta, Rf_nrows(beta), k, "beta");
+  check(nngp_design_commit_chains(c, as_int(mask), sh, bo, bn, b0, b), c);
+  return R_NilValue;
+}
+
+SEXP C_nngp_get_mu(SEXP p) {
+  nngp_ctx* c = get_ctx(p);
+  nngp_info inf;
+  check(nngp_ctx_info(c, &inf), c);
+  SEXP mu = PROTECT(Rf_allocVector(REALSXP, inf.n_obs));
+  const int rc = nngp_get_mu(c, REAL(mu));
+  UNPROTECT(1);
+  check(rc, c);
+  return mu;
+}
+
 /* ---------- registration ---------- */
 #define E(name, n) {#name, (DL_FUNC)&name, n}
 SEXP C_nngp_ancillary_step_chains(SEXP p, SEXP mask, SEXP covfun, SEXP covparms, SEXP beta0, SEXP dls, SEXP lnv) {
@@ -829,6 +917,11 @@ static const R_CallMethodDef call_methods[] = {
     E(C_nngp_sufficient_step_chains, 7),
     E(C_nngp_field_response_ratio_chains, 4),
     E(C_nngp_sum_squared_residuals_chains, 3),
+    E(C_nngp_design_set, 4),
+    E(C_nngp_design_mean_stats_chains, 4),
+    E(C_nngp_design_interweave_stats_chains, 4),
+    E(C_nngp_design_commit_chains, 7),
+    E(C_nngp_get_mu, 1),
     {NULL, NULL, 0}};
 #undef E
 
