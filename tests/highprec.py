@@ -201,6 +201,37 @@ def vecchia_linv_hp(covfun, cp, locs, NN):
     return out
 
 
+def pad_na(NN, b):
+    """NN with trailing all-NA columns up to b columns (find_ordered_nn stores
+    min(m, n - 1) + 1 columns; GpGp keeps m + 1, the rest NA)"""
+    NN = np.asarray(NN, np.int32)
+    return np.column_stack([NN, np.full((NN.shape[0], max(0, b - NN.shape[1])), NA, np.int32)])
+
+
+def sparse_B_times(Linv, NN, x, x_abs=None):
+    """(B x, |B| x_abs) in longdouble for the sparse factor B[i, NN[i, g] - 1] =
+    Linv[i, g] (NN 1-based with NA entries, as the oracle's dense_B reads it),
+    without forming the n x n matrix: one vectorised pass per neighbour column
+    g, NA entries masked out.  x is a vector (n,) or a matrix (n, k); x_abs
+    defaults to |x| (pass the sum of absolute values where x is itself a sum).
+    tests/test_highprec_reference.py holds it to dense_B."""
+    Linv, NN = np.asarray(Linv).astype(LD), np.asarray(NN)
+    x = np.asarray(x).astype(LD)
+    x_abs = np.abs(x) if x_abs is None else np.asarray(x_abs).astype(LD)
+    n, b = NN.shape
+    assert Linv.shape == (n, b) and x.shape[0] == n and x_abs.shape == x.shape
+    tail = (1,) * (x.ndim - 1)
+    out, out_abs = np.zeros(x.shape, LD), np.zeros(x.shape, LD)
+    for g in range(b):
+        ok = NN[:, g] != NA
+        idx = np.where(ok, NN[:, g], 1).astype(np.int64) - 1
+        assert idx.min() >= 0 and idx.max() < n
+        l = np.where(ok, Linv[:, g], LD(0)).reshape((n,) + tail)
+        out += l * x[idx]
+        out_abs += np.abs(l) * x_abs[idx]
+    return out, out_abs
+
+
 def row_conds(O, covfun, cp, locs, NN):
     """cond(C_i) of every row's local covariance, from the oracle's double
     covariance (as test_gpu_parity._assert_rows_close takes it)"""

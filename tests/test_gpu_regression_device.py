@@ -2,7 +2,10 @@
 145-151,226-250): the three array operations against numpy with a-priori
 rounding bounds, their bitwise rules (chain mask, run to run), the state a
 commit leaves, the refreshed bookkeeping, and full Gibbs iterations with
-regression="device" against the CPU oracle.
+regression="device" against the CPU oracle.  The primitives here run at one
+shape (500 locations, 550 observations, m = 6, 3 chains);
+tests/test_gpu_regression_shapes.py takes the same checks over the launch
+shapes and limits.
 
 Bounds: a sum of k floating-point operations on its longest path differs from
 the exact value by at most gamma_k x the sum of the absolute values of the
@@ -13,6 +16,7 @@ import copy
 import numpy as np
 import pytest
 
+import highprec as H
 from conftest import make_problem
 
 pytestmark = pytest.mark.gpu
@@ -21,15 +25,24 @@ LD = np.longdouble
 U = 2.0 ** -53
 EPS = np.finfo(np.float64).eps
 COV = "exponential_isotropic"
-CPS = [[1.0, 0.10, 0.0], [1.2, 0.07, 0.05], [0.8, 0.15, 0.0]]
+CPS = [[1.0, 0.10, 0.0], [1.2, 0.07, 0.05], [0.8, 0.15, 0.0], [0.9, 0.12, 0.02]]
 
 
-def _synthetic(P, p, locs_cols0, n=500, m=6, seed=3):
+def _synthetic(P, p, locs_cols0, n=500, m=6, seed=3, n_obs=None):
     """make_problem(n=500, m=6, dup_frac=0.1): 550 observations in shuffled
     order (first_obs is not the identity), p centred columns, the columns
-    locs_cols0 constant within a location."""
+    locs_cols0 constant within a location.  With n_obs: every location once,
+    then n_obs - n random repeats.  The NNarray keeps m + 1 columns (all NA
+    beyond n - 1 neighbours), so b = m + 1 also where n <= m."""
     assert np.finfo(LD).eps < 2.0 ** -60
-    locs, NN, col, lm, y = make_problem(P, n, m, seed=seed, dup_frac=0.1)
+    if n_obs is None:
+        locs, NN, col, lm, y = make_problem(P, n, m, seed=seed, dup_frac=0.1)
+    else:
+        locs, NN, col, lm, _ = make_problem(P, n, m, seed=seed)
+        rep = np.random.default_rng(seed + 200)
+        lm = np.concatenate([lm, rep.integers(1, n + 1, n_obs - n).astype(np.int32)])
+        y = rep.normal(size=n_obs)
+    NN = H.pad_na(NN, m + 1)
     rng = np.random.default_rng(seed + 100)
     perm = rng.permutation(len(lm))
     lm, y = lm[perm], y[perm] + 2.0
@@ -37,7 +50,7 @@ def _synthetic(P, p, locs_cols0, n=500, m=6, seed=3):
     for c in locs_cols0:
         X[:, c] = rng.normal(size=n)[lm - 1]
     X = X - X.mean(0)
-    first_obs = np.array([np.nonzero(lm == i + 1)[0][0] + 1 for i in range(n)], np.int32)
+    first_obs = (np.unique(lm, return_index=True)[1] + 1).astype(np.int32)  # all of 1..n occur
     return {"locs": locs, "NN": NN, "col": col, "lm": lm, "y": y, "X": X, "first_obs": first_obs,
             "locs_cols": list(locs_cols0), "n": n, "m": m}
 
@@ -62,34 +75,40 @@ def _open(P, pr, C=3, design=True):
     return ctx
 
 
-def _primitives(P, pr, inp, masks):
+def _primitives_on(ctx, pr, inp, masks):
     """Every primitive for the chain masks `masks` (together they cover all
-    chains) on a fresh context -> per-chain results."""
+    chains) on the context `ctx`, which holds the design -> per-chain results."""
     C = len(inp["fields"])
     ql = len(pr["locs_cols"])
     out = {k: [None] * C for k in ("mean", "t", "gram", "refreshed", "field", "mu", "linv")}
-    with _open(P, pr, C) as ctx:
-        for k in range(C):
-            ctx.select(k).factor(0, COV, CPS[k])
-            ctx.set_field(inp["fields"][k])
-            out["linv"][k] = ctx.get_linv(0)
-        for mask in masks:
-            ks = [k for k in range(C) if (mask >> k) & 1]
-            mean = ctx.design_mean_stats_chains(mask, inp["b0"])
+    for k in range(C):
+        ctx.select(k).factor(0, COV, CPS[k])
+        ctx.set_field(inp["fields"][k])
+        out["linv"][k] = ctx.get_linv(0)
+    for mask in masks:
+        ks = [k for k in range(C) if (mask >> k) & 1]
+        mean = ctx.design_mean_stats_chains(mask, inp["b0"])
+        if ql:
+            t, gram, refreshed = ctx.design_interweave_stats_chains(mask, inp["shift"], inp["bl_old"])
+        ctx.design_commit_chains(mask, inp["shift"], inp["bl_old"], inp["bl_new"], inp["b0_new"], inp["beta"])
+        for k in ks:
+            out["mean"][k] = mean[k].copy()
             if ql:
-                t, gram, refreshed = ctx.design_interweave_stats_chains(mask, inp["shift"], inp["bl_old"])
-            ctx.design_commit_chains(mask, inp["shift"], inp["bl_old"], inp["bl_new"], inp["b0_new"], inp["beta"])
-            for k in ks:
-                out["mean"][k] = mean[k].copy()
-                if ql:
-                    out["t"][k], out["gram"][k], out["refreshed"][k] = t[k].copy(), gram[k].copy(), int(refreshed[k])
-                out["field"][k] = ctx.select(k).get_field()
-                out["mu"][k] = ctx.get_mu()
+                out["t"][k], out["gram"][k], out["refreshed"][k] = t[k].copy(), gram[k].copy(), int(refreshed[k])
+            out["field"][k] = ctx.select(k).get_field()
+            out["mu"][k] = ctx.get_mu()
     return out
 
 
+def _primitives(P, pr, inp, masks):
+    """_primitives_on a fresh context"""
+    with _open(P, pr, len(inp["fields"])) as ctx:
+        return _primitives_on(ctx, pr, inp, masks)
+
+
 def _reference(O, pr, inp, linv, k):
-    """Chain k in long double, with the sums of absolute values the bounds use."""
+    """Chain k in long double, with the sums of absolute values the bounds use;
+    B stays sparse (highprec.sparse_B_times), so n is not limited by an n x n matrix."""
     lm0 = pr["lm"] - 1
     X, y, f = pr["X"].astype(LD), pr["y"].astype(LD), inp["fields"][k].astype(LD)
     X1 = np.column_stack([np.ones(len(y), LD), X])
@@ -97,12 +116,12 @@ def _reference(O, pr, inp, linv, k):
     ref = {"mean": resid @ X1, "mean_abs": (np.abs(y) + np.abs(f[lm0]) + abs(inp["b0"][k])) @ np.abs(X1)}
     Xl = X[pr["first_obs"] - 1][:, pr["locs_cols"]]
     Xl1 = np.column_stack([np.ones(pr["n"], LD), Xl])
-    B = O.dense_B(linv, pr["NN"]).astype(LD)
     bo, bn, sh = inp["bl_old"][k].astype(LD), inp["bl_new"][k].astype(LD), LD(inp["shift"][k])
     other = f + sh + Xl @ bo
     other_abs = np.abs(f) + abs(sh) + np.abs(Xl) @ np.abs(bo)
-    SX, SX_abs = B @ Xl1, np.abs(B) @ np.abs(Xl1)
-    ref.update({"t": (B @ other) @ SX, "t_abs": (np.abs(B) @ other_abs) @ SX_abs,
+    SX, SX_abs = H.sparse_B_times(linv, pr["NN"], Xl1)
+    Bo, Bo_abs = H.sparse_B_times(linv, pr["NN"], other, other_abs)
+    ref.update({"t": Bo @ SX, "t_abs": Bo_abs @ SX_abs,
                 "gram": SX.T @ SX, "gram_abs": SX_abs.T @ SX_abs,
                 "field": other - Xl @ bn, "field_abs": other_abs + np.abs(Xl) @ np.abs(bn),
                 "mu": LD(inp["b0_new"][k]) + X @ inp["beta"][k].astype(LD),
@@ -265,9 +284,12 @@ def test_iterations_match_oracle_vignette_X_locs(P, O, toy):
     _compare(res, ref)
 
 
-def _synthetic_run(P, pr, iters=10, nc=3):
+def _synthetic_run(P, pr, iters=10, nc=3, n_chains=1):
+    """Chain i of n_chains against the oracle's chain i.  One chain runs alone
+    (_run_chain); several run in lockstep on one context, so the regression
+    calls are batched over the chains."""
     import mcmc_oracle as MO
-    from nngp_amd.update_gaussian import _philox_key, _run_chain
+    from nngp_amd.update_gaussian import _philox_key, _run_chain, mcmc_nngp_update_Gaussian
 
     n, p = pr["n"], pr["X"].shape[1]
     X1 = np.column_stack([np.ones(len(pr["y"])), pr["X"]])
@@ -277,22 +299,35 @@ def _synthetic_run(P, pr, iters=10, nc=3):
           "obs_per_loc": np.bincount(pr["lm"] - 1, minlength=n).astype(np.int32), "hctam_scol_1": pr["first_obs"]}
     stm = {"covfun": {"stationary_covfun": COV, "shape_params": ["log_range"]}}
     rng = np.random.default_rng(0)
-    state = {"params": {"beta_0": 2.0, "beta": np.zeros(p), "log_scale": 0.0, "shape": np.array([np.log(0.1)]),
-                        "log_noise_variance": np.log(0.5), "field": 2.0 + rng.normal(size=n)},
-             "transition_kernels": {"covariance_params_sufficient": {"logvar": -2.0},
-                                    "covariance_params_ancillary": {"logvar": -2.0},
-                                    "log_noise_variance": {"logvar": -1.0}}}
-    with P.ChainContext(pr["locs"], pr["NN"], pr["col"], pr["lm"], pr["y"], device=0) as ctx:
-        res = _run_chain(0, copy.deepcopy(state), ctx, X, pr["y"], stm, va, iters, 1.0, True, nc, 0, 1,
-                         regression="device")
-    ref = MO.run_chain(0, state, pr["locs"], pr["NN"], pr["col"], X, pr["y"], stm, va, iters, 1.0, nc, 0,
-                       _philox_key(0, 1, 1))
-    _compare(res, ref)
+    states = [{"params": {"beta_0": 2.0, "beta": np.zeros(p), "log_scale": 0.0, "shape": np.array([np.log(0.1)]),
+                          "log_noise_variance": np.log(0.5), "field": 2.0 + rng.normal(size=n)},
+               "transition_kernels": {"covariance_params_sufficient": {"logvar": -2.0},
+                                      "covariance_params_ancillary": {"logvar": -2.0},
+                                      "log_noise_variance": {"logvar": -1.0}}} for _ in range(n_chains)]
+    with P.ChainContext(pr["locs"], pr["NN"], pr["col"], pr["lm"], pr["y"], device=0, n_chains=n_chains) as ctx:
+        if n_chains == 1:
+            res = [_run_chain(0, copy.deepcopy(states[0]), ctx, X, pr["y"], stm, va, iters, 1.0, True, nc, 0, 1,
+                              regression="device")]
+        else:
+            out = mcmc_nngp_update_Gaussian(pr["locs"], X, pr["y"], stm, va, copy.deepcopy(states), iters,
+                                            field_thinning=1.0, n_chromatic=nc, seed=1, regression="device",
+                                            contexts=[ctx.view(i) for i in range(n_chains)])
+            res = list(out.values())
+    for i, state in enumerate(states):
+        ref = MO.run_chain(i, state, pr["locs"], pr["NN"], pr["col"], X, pr["y"], stm, va, iters, 1.0, nc, 0,
+                           _philox_key(0, i + 1, 1))
+        _compare(res[i], ref)
 
 
 def test_iterations_match_oracle_synthetic_design(P, O, prob):
     """p = 70 with three interweaved columns, 10 iterations."""
     _synthetic_run(P, prob)
+
+
+def test_iterations_match_oracle_row_group_32(P, O):
+    """m = 16 (b = 17: the 32-lane row group), n = 600, p = 3 with one
+    interweaved column, two chains in lockstep on one context, 10 iterations."""
+    _synthetic_run(P, _synthetic(P, 3, [1], n=600, m=16, seed=7), n_chains=2)
 
 
 def test_iterations_match_oracle_X_obs_only(P, O):

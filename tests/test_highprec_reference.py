@@ -96,3 +96,34 @@ def test_short_rows_and_failing_row(O):
                 lambda nn: O.vecchia_linv("exponential_isotropic", [1.0, 1.0, -1e-3], locs, nn[:, :2])):
         with pytest.raises(np.linalg.LinAlgError, match="row 18$"):
             ref(NN)
+
+
+@pytest.mark.parametrize("n,m", [(500, 6), (5, 10)])
+def test_sparse_B_times_equals_dense_B(P, O, n, m):
+    """B x and |B| |x| straight from (Linv, NN) against the oracle's dense B in
+    long double, a vector and a 3-column matrix; at n = 5, m = 10 the NNarray
+    keeps its m + 1 = 11 columns, so every row is short.  NA entries of Linv
+    hold a nonzero value here: both sides must mask them by NN, not by value.
+    Bound: either side sums at most b products per entry in long double, in its
+    own order: 2 b 2^-64 x the sum of the absolute values of the products."""
+    from conftest import make_problem
+
+    locs, NN, _, _, _ = make_problem(P, n, m, seed=4)
+    NN = H.pad_na(NN, m + 1)
+    assert NN.shape == (n, m + 1) and (n > m or np.all((NN == O.NA).any(axis=1)))
+    linv = H.vecchia_linv_hp("exponential_isotropic", [1.2, 0.07, 0.05], locs, NN).astype(np.float64)
+    linv[NN == O.NA] = 7.0
+    rng = np.random.default_rng(n)
+    B = O.dense_B(linv, NN).astype(H.LD)
+    for x in (rng.normal(size=n), rng.normal(size=(n, 3))):
+        got, got_abs = H.sparse_B_times(linv, NN, x)
+        want, want_abs = B @ x.astype(H.LD), np.abs(B) @ np.abs(x).astype(H.LD)
+        assert got.shape == x.shape and got.dtype == H.LD
+        bound = 2 * (m + 1) * H.LD(2.0) ** -64 * want_abs
+        assert np.all(want_abs > 0)
+        assert np.all(np.abs(got - want) <= bound), float(np.max(np.abs(got - want) / bound))
+        assert np.all(np.abs(got_abs - want_abs) <= bound)
+    # x_abs given: |B| x_abs
+    xa = np.abs(rng.normal(size=n)) + 1.0
+    _, got_abs = H.sparse_B_times(linv, NN, rng.normal(size=n), xa)
+    assert np.all(np.abs(got_abs - np.abs(B) @ xa.astype(H.LD)) <= 2 * (m + 1) * H.LD(2.0) ** -64 * got_abs)
