@@ -250,7 +250,15 @@ struct nngp_ctx {
   int lds_max = 0;                // LDS bytes per CU of the device
   double* rg_d = nullptr;         // sum of the tiles' local rows x C
   unsigned* ctl_d = nullptr;      // [0] call id, [1] timeout word of a launch, [2] sticky timeout (tiles.hip)
-  unsigned* tmo_h = nullptr;      // pinned copy of the sticky timeout word after each launch
+  unsigned* tmo_h = nullptr;      // pinned copy of the sticky timeout word (after each launch, or read at the sync)
+  // one-launch calls (one GPU, no shard; NNGP_SWEEP_GRAPH=1: off): a warm call
+  // is one stream operation, the tile launch -- the chains' scalars and the
+  // call id are its arguments (TileCall), no bump kernel, no
+  // scalar upload, no copy of the timeout word behind it (tile_timeout_check)
+  bool one_launch = false;
+  unsigned tile_call_n = 0;       // call ids of those launches: kTileArgCall | 1 .. 2^31 - 1, then again from 1
+  bool tmo_unread = false;        // such a launch since tmo_h was last read from the device
+  bool scal_dirty = false;        // scal_h changed since the last upload (ensure_scalars)
   int inject_tmo = 0;             // tests (NNGP_TILE_INJECT_TIMEOUT=k): the first k sweep calls report a timeout
   unsigned long long* tdbg_d = nullptr;  // NNGP_PROBE=9: per-tile phase times, =2: per-phase timeline
   size_t tdbg_n = 0;
@@ -340,8 +348,15 @@ hipError_t upload(T* dst, const T* src, size_t count, hipStream_t st) {
 }
 
 // (after a host sync) the sticky timeout word of the launches since the last
-// check: reported once, then cleared on the device too
+// check: reported once, then cleared on the device too.  One-launch calls put
+// no copy of the word behind their launch: it is fetched here, where it is
+// consumed (the launches have drained: 4 bytes, no wait).
 static int tile_timeout_check(nngp_ctx* c) {
+  if (c->engine == 1 && c->tmo_unread) {
+    c->tmo_unread = false;
+    HIPCHK(c, hipMemcpyAsync(c->tmo_h, c->ctl_d + 2, sizeof(unsigned), hipMemcpyDeviceToHost, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+  }
   if (c->engine == 1 && c->tmo_h && *c->tmo_h != 0) {
     *c->tmo_h = 0;
     HIPCHK(c, hipMemsetAsync(c->ctl_d + 2, 0, sizeof(unsigned), c->st));
@@ -938,6 +953,10 @@ static int ctx_create(const double* locs, int n, int d, const int* NNarray, int 
         {
           const char* sw = std::getenv("NNGP_SWEEP_WARM");
           c->warm_on = shard_G == 0 && !(sw && std::string(sw) == "0");
+          // NNGP_SWEEP_GRAPH=1: the captured-graph call (bump kernel, scalar
+          // upload and timeout copy per call) instead of the one-launch call
+          const char* sg = std::getenv("NNGP_SWEEP_GRAPH");
+          c->one_launch = shard_G == 0 && !(sg && std::string(sg) == "1");
         }
         c->engine_note = "tiles: " + std::to_string(T) + " tiles of " + std::to_string(NT) + " threads, " +
                          std::to_string(c->tresident) + " resident per CU x " + std::to_string(cus) + " CUs" +
@@ -1931,7 +1950,19 @@ static int sweep_prepare(nngp_ctx* c, int k, double beta0, double log_scale, dou
   sc.dshift = 0.0;
   sc.seed = seed;
   sc.counter_base = counter_base;
+  c->scal_dirty = true;
   return NNGP_OK;
+}
+
+// a call on the chains of mask: no shift staged by an earlier call for a chain
+// outside it may be left in the scalars (a single-chain call prepares its own
+// chain only; the tile prologue would move that chain's w and r again)
+static void clear_unswept_shifts(nngp_ctx* c, int mask) {
+  for (int k = 0; k < c->C; ++k)
+    if (!((mask >> k) & 1) && c->scal_h[k].dshift != 0.0) {
+      c->scal_h[k].dshift = 0.0;
+      c->scal_dirty = true;
+    }
 }
 
 // a sweep call rewrites the fields of the chains in mask (row-statistics cache)
@@ -1952,7 +1983,23 @@ static int upload_scalars(nngp_ctx* c) {
   std::memcpy(slot, c->scal_h, sizeof(SweepScalars) * c->C);
   HIPCHK(c, hipMemcpyAsync(c->scal_d, slot, sizeof(SweepScalars) * c->C, hipMemcpyHostToDevice, c->st));
   HIPCHK(c, hipEventRecord(c->scal_ev[r], c->st));
+  c->scal_dirty = false;
   return NNGP_OK;
+}
+
+// scal_d is read by field_to_slots_multi, spmv_chains and slots_to_field_multi
+// (a cold call's prologue, an epilogue of its own), the colour engine's
+// launches (normals, colours, shard ghosts) and every tile launch that does
+// not carry the scalars as arguments (captured graphs: NNGP_SWEEP_GRAPH=1,
+// sweep_timed; injected normals; shards).  Before any of them: the upload, if
+// scal_h changed since the last one (sweep_prepare, stage_warm_shift,
+// clear_unswept_shifts).  A warm one-launch call reads none of it and skips it.
+static int ensure_scalars(nngp_ctx* c) { return c->scal_dirty ? upload_scalars(c) : NNGP_OK; }
+
+// call id of the next one-launch call (TileCall::call): never 0
+static unsigned next_tile_call(nngp_ctx* c) {
+  c->tile_call_n = c->tile_call_n % (kTileArgCall - 1u) + 1u;
+  return kTileArgCall | c->tile_call_n;
 }
 
 // A sweep call = prologue (per chain in mask: w = field - beta0 in compact
@@ -1964,7 +2011,10 @@ static int upload_scalars(nngp_ctx* c) {
 // holds other ranks' slots) and the colour engine keep the kernel.
 enum SweepPart { kPrologue = 1, kColours = 2, kEpilogue = 4, kAll = 7 };
 
-static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double* z_dev, int parts = kAll) {
+// direct (one-launch calls, never inside a capture): the tile launch takes
+// the scalars and its call id as arguments and nothing follows it.
+static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double* z_dev, int parts = kAll,
+                              bool direct = false) {
   const int n = c->n;
   SweepDev L = sweep_dev(c);
   FieldPtrs fp;
@@ -1993,9 +2043,15 @@ static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double*
       a.slot_dpos = c->slot_dpos_d;
       a.field = fp;
     }
+    TileCall tc;
+    if (direct) {
+      tc.call = next_tile_call(c);
+      for (int k = 0; k < c->C; ++k) tc.scal[k] = c->scal_h[k];
+    }
     HIPCHK(c, launch_sweep_tiles(c->st, tile_dev(c), a, c->tl.max_rows, c->tl.NTK, c->tl.max_batches,
-                                  c->tl.max_gslots));
-    HIPCHK(c, hipMemcpyAsync(c->tmo_h, c->ctl_d + 2, sizeof(unsigned), hipMemcpyDeviceToHost, c->st));
+                                  c->tl.max_gslots, nullptr, 0, nullptr, direct ? &tc : nullptr));
+    if (direct) c->tmo_unread = true;  // the sticky word is fetched at the next sync (tile_timeout_check)
+    else HIPCHK(c, hipMemcpyAsync(c->tmo_h, c->ctl_d + 2, sizeof(unsigned), hipMemcpyDeviceToHost, c->st));
   }
   if ((parts & kColours) && c->engine == 0) {
     const size_t zn = (size_t)n * c->C;
@@ -2015,8 +2071,11 @@ static int enqueue_sweep_body(nngp_ctx* c, int n_sweeps, int mask, const double*
       }
     }
   }
-  if ((parts & kEpilogue) && !fused)
+  if ((parts & kEpilogue) && !fused) {
+    int rc;
+    if (direct && (rc = ensure_scalars(c))) return rc;
     HIPCHK(c, launch_slots_to_field_multi(c->st, c->n, c->slot_dpos_d, fp, c->scal_d, c->w_slot_d, c->C, mask));
+  }
   return NNGP_OK;
 }
 
@@ -2087,9 +2146,22 @@ static int stage_warm_shift(nngp_ctx* c, int shift, const double* beta0) {
 // the call's launches: one captured graph of the whole call when every chain
 // is cold; else the prologue graph of the cold chains and the graph of the
 // colours + epilogue (warm and shifted chains start from the last call's w, r)
+// One-launch contexts: the prologue graph of the cold chains (after the
+// scalar upload it reads), then the tile launch itself, not a graph -- a
+// replayed graph freezes the arguments the scalars and the call id travel in,
+// and a graph of one kernel saves nothing.
 static int enqueue_call(nngp_ctx* c, int n_sweeps, int mask, int cold) {
   hipGraphExec_t ex;
   int rc;
+  if (c->one_launch) {
+    if (cold) {
+      if ((rc = ensure_scalars(c))) return rc;
+      if ((rc = graph_for(c, n_sweeps, cold, &ex, kPrologue))) return rc;
+      HIPCHK(c, hipGraphLaunch(ex, c->st));
+    }
+    return enqueue_sweep_body(c, n_sweeps, mask, nullptr, kColours | kEpilogue, true);
+  }
+  if ((rc = ensure_scalars(c))) return rc;
   if (cold == mask) {
     if ((rc = graph_for(c, n_sweeps, mask, &ex, kAll))) return rc;
     HIPCHK(c, hipGraphLaunch(ex, c->st));
@@ -2143,8 +2215,10 @@ int nngp_sweep(nngp_ctx* c, int n_sweeps, double beta0, double log_scale, double
   fields_written(c, mask);
   if ((rc = sweep_prepare(c, k, beta0, log_scale, lnv, seed, counter_base))) return rc;
   if (shift && (rc = stage_warm_shift(c, shift, b0v))) return rc;
+  clear_unswept_shifts(c, mask);
   if ((rc = flush_sweep_values(c, mask))) return rc;
-  if ((rc = upload_scalars(c))) return rc;
+  // (a one-launch call uploads the scalars only if something reads them: enqueue_call)
+  if ((z || sharded_call(c)) && (rc = ensure_scalars(c))) return rc;
   if (sharded_call(c)) {
     if (z) return fail_msg(c, NNGP_ERR_ARG, "sweep: injected normals are not supported on shard contexts");
     return shard_call(c, n_sweeps, mask);
@@ -2208,7 +2282,7 @@ int nngp_sweep_chains(nngp_ctx* c, int n_sweeps, const double* beta0, const doub
     if ((rc = sweep_prepare(c, k, beta0[k], log_scale[k], lnv[k], seed[k], counter_base[k]))) return rc;
   if (shift && (rc = stage_warm_shift(c, shift, beta0))) return rc;
   if ((rc = flush_sweep_values(c, all))) return rc;
-  if ((rc = upload_scalars(c))) return rc;
+  if (sharded_call(c) && (rc = ensure_scalars(c))) return rc;
   if (sharded_call(c)) return shard_call(c, n_sweeps, all);
   // the device's tile lock around the launch (and, unless the call returns
   // without a sync, until it has drained)
@@ -2619,7 +2693,7 @@ static int tile_group_call(nngp_ctx** ctxs, int G, int n_sweeps, const double* b
     for (int k = 0; k < c->C; ++k)
       if ((rc = sweep_prepare(c, k, beta0[k], log_scale[k], lnv[k], seed[k], counter_base[k]))) { cleanup(); return rc; }
     if ((rc = flush_sweep_values(c, mask))) { cleanup(); return rc; }
-    if ((rc = upload_scalars(c))) { cleanup(); return rc; }
+    if ((rc = ensure_scalars(c))) { cleanup(); return rc; }
     if ((rc = enqueue_sweep_body(c, n_sweeps, mask, nullptr, kPrologue))) { cleanup(); return rc; }
     GCHK(c, launch_tile_call_bump(c->st, c->ctl_d));  // every rank's call id and timeout word
     GCHK(c, hipEventRecord(ev[g], c->st));
@@ -2711,7 +2785,7 @@ int nngp_sweep_chains_group(nngp_ctx** ctxs, int G, int n_sweeps, const double* 
     for (int k = 0; k < c->C; ++k)
       if ((rc = sweep_prepare(c, k, beta0[k], log_scale[k], lnv[k], seed[k], counter_base[k]))) return rc;
     if ((rc = flush_sweep_values(c, mask))) return rc;
-    if ((rc = upload_scalars(c))) return rc;
+    if ((rc = ensure_scalars(c))) return rc;
     if ((rc = enqueue_sweep_body(c, n_sweeps, mask, nullptr, kPrologue))) return rc;
   }
   // ev_own[g]: rank g's segment of the colour is written; ev_done[g]: rank g
@@ -2787,7 +2861,7 @@ int nngp_sweep_timed(nngp_ctx* c, int n_sweeps, const double* beta0, const doubl
   for (int k = 0; k < c->C; ++k)
     if ((rc = sweep_prepare(c, k, beta0[k], log_scale[k], lnv[k], seed[k], counter_base[k]))) return rc;
   if ((rc = flush_sweep_values(c, (1 << c->C) - 1))) return rc;
-  if ((rc = upload_scalars(c))) return rc;
+  if ((rc = ensure_scalars(c))) return rc;
   const int mask = (1 << c->C) - 1;
   std::unique_lock<std::mutex> tlk;
   if (c->engine == 1) tlk = std::unique_lock<std::mutex>(tile_lock(c->device));

@@ -235,7 +235,7 @@ struct TileDev {
   double* rg;                 // tiles with r in global memory: local rows x C (null: r in LDS)
   const SweepScalars* scal;   // C
   const double* const* b1;    // C: B 1 of each chain's current factor (device rows; read when scal.dshift != 0)
-  unsigned* ctl;              // [0] call id (bumped on the device before every launch), [1] timeout word
+  unsigned* ctl;              // [0] call id (launches without a TileCall: bumped on the device), [1] timeout word
   unsigned long long* dbg;    // NNGP_PROBE=9 / 2: per-tile phase times / per-phase timeline, else null
   int K, C, T, n;
   int max_gslots;             // max foreign slots of a (tile, colour): LDS of their dw
@@ -258,6 +258,23 @@ struct TileLaunch {
   const int* slot_dpos = nullptr;
   FieldPtrs field = {};
 };
+// One-launch calls (one GPU, launched directly: a replayed graph would freeze
+// them): call != 0 is the launch's call id and scal the chains' scalars, both
+// read from the kernel arguments -- nothing reads TileDev::scal or ctl[0], and
+// no bump kernel runs before the launch.  These ids have kTileArgCall set
+// (capi.hip next_tile_call); the ids a bump kernel counts up from 0 in ctl[0]
+// (launches inside captured graphs, injected normals, shards) do not, so
+// granules of a launch of one kind never match a launch of the other kind in
+// the same context.  call == 0 (or no TileCall): the scalars from
+// TileDev::scal, the id from ctl[0] / TileShard::call.
+// (An argument of its own, read where it is used: as members of TileLaunch,
+// which the kernel copies at entry, the scalars stayed in registers through
+// the phase loop and spilled.)
+struct TileCall {
+  unsigned call = 0;
+  SweepScalars scal[kMaxChains] = {};
+};
+constexpr unsigned kTileArgCall = 0x80000000u;
 
 // cells per thread of an own batch (the layout's RMAX): two batches of C
 // chains stay in registers (C >= 3: fewer cells per batch)
@@ -286,7 +303,7 @@ struct TileShard {
 // would launch that are resident on one CU at once (occupancy query)
 hipError_t launch_sweep_tiles(hipStream_t st, const TileDev& D, const TileLaunch& a, int max_rows, int NT,
                               int max_batches, int max_gslots, const TileShard* sh = nullptr, int grid = 0,
-                              int* occ = nullptr);
+                              int* occ = nullptr, const TileCall* call = nullptr);
 // ctl[0] += 1 (call id), ctl[1] = 0 (timeout word): before every launch of a rank
 hipError_t launch_tile_call_bump(hipStream_t st, unsigned* ctl);
 // tests: the control words a launch whose tiles timed out leaves behind

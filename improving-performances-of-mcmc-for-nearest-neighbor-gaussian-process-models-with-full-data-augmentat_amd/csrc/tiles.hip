@@ -33,9 +33,11 @@ namespace nngp {
 // update a row twice within a colour.  j's granule is rewritten one sweep
 // later, after its owner has read granules of every tile reading j (they
 // share the row, so each is the other's neighbour at its own colour), so no
-// reader sees a later value; the call id (bumped on the device before every
+// reader sees a later value; the call id (an argument of the launch on
+// one-launch calls, kernels.h TileCall; else bumped on the device before the
 // launch) keeps granules of earlier calls from matching.  Spins are bounded: a
-// timeout sets ctl[1] and the launch drains (the host reports an error).
+// timeout stores the call id into ctl[1] and the launch drains (the host
+// reports an error).
 // the cell / slot encoding of the host layout (graph_prep.h), one definition
 constexpr uint32_t kTPad = kTilePadRow;
 constexpr uint32_t kTStart = kCellStart, kTEnd = kCellEnd;
@@ -67,8 +69,9 @@ hipError_t launch_set_ptr(hipStream_t st, const double** dst, int k, const doubl
   return hipGetLastError();
 }
 
-// ctl: [0] call id, [1] the launch's timeout word (its tiles stop waiting once
-// it is set), [2] the sticky copy the host reads: a timeout stays reported
+// ctl: [0] call id of the launches that take it from here (the bump below),
+// [1] the launch's timeout word (its tiles stop waiting once it carries their
+// call id), [2] the sticky copy the host reads: a timeout stays reported
 // until the host has seen it (capi.hip tile_timeout_check clears it), however
 // many launches follow before the next host sync
 __global__ void tile_call_bump_kernel(unsigned* ctl) {
@@ -76,14 +79,20 @@ __global__ void tile_call_bump_kernel(unsigned* ctl) {
   ctl[1] = 0u;   // timeout word of this launch
 }
 
-__device__ __forceinline__ void tile_timeout_raise(unsigned* tmo) {
-  __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+// tag: what the launch's timeout word is set to.  The tiles of a sweep launch
+// store their call id and stop waiting once the word equals it, so a word left
+// by an earlier launch needs no reset (one-launch calls run no bump kernel);
+// the one-thread kernels below store 1, which no such launch waits on (a
+// bumped id of 1 is preceded by the bump's reset, argument ids have
+// kTileArgCall set)
+__device__ __forceinline__ void tile_timeout_raise(unsigned* tmo, unsigned tag) {
+  __hip_atomic_store(tmo, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_store(tmo + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // tests (NNGP_TILE_INJECT_TIMEOUT=k: after each of the first k sweep calls of
 // a context): what a launch whose tiles timed out leaves in ctl
-__global__ void tile_inject_timeout_kernel(unsigned* ctl) { tile_timeout_raise(ctl + 1); }
+__global__ void tile_inject_timeout_kernel(unsigned* ctl) { tile_timeout_raise(ctl + 1, 1u); }
 
 hipError_t launch_tile_inject_timeout(hipStream_t st, unsigned* ctl) {
   hipLaunchKernelGGL(tile_inject_timeout_kernel, dim3(1), dim3(1), 0, st, ctl);
@@ -112,7 +121,7 @@ __global__ void tile_xwait_kernel(const unsigned* __restrict__ xflag, unsigned* 
     for (unsigned spins = 0;; ++spins) {
       if (__hip_atomic_load(xflag + h, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) == call) break;
       if (spins > (1u << 22)) {
-        tile_timeout_raise(ctl + 1);
+        tile_timeout_raise(ctl + 1, 1u);
         break;
       }
       __builtin_amdgcn_s_sleep(2);
@@ -746,8 +755,8 @@ __device__ __forceinline__ void tile_phase(const TileDev& D, const TileLaunch& a
         // bounded wait (about a second per poll); once any tile of the launch
         // has given up (timeout word), the others stop waiting within ~1k polls
         if (S.timed_out || spins > (1u << 20) ||
-            ((spins & 1023u) == 1023u && __hip_atomic_load(S.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          if (!S.timed_out) tile_timeout_raise(S.tmo);
+            ((spins & 1023u) == 1023u && __hip_atomic_load(S.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == S.call)) {
+          if (!S.timed_out) tile_timeout_raise(S.tmo, S.call);
           S.timed_out = true;
           break;
         }
@@ -1114,8 +1123,8 @@ __device__ __forceinline__ void tile_phase_xw(const TileDev& D, TileState& S, in
       // bounded wait (about a second per poll); once any tile of the launch
       // has given up (timeout word), the others stop waiting within ~1k polls
       if (S.timed_out || spins > (1u << 20) ||
-          ((spins & 1023u) == 1023u && __hip_atomic_load(S.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-        if (!S.timed_out) tile_timeout_raise(S.tmo);
+          ((spins & 1023u) == 1023u && __hip_atomic_load(S.tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == S.call)) {
+        if (!S.timed_out) tile_timeout_raise(S.tmo, S.call);
         S.timed_out = true;
 #pragma unroll
         for (int k = 0; k < PB; ++k)
@@ -1229,7 +1238,8 @@ __device__ __forceinline__ void tile_phase_cells(const TileDev& D, const TileLau
 // workgroup batches, XW = 0 with IB: DESIGN.md §3; IB is left with XW = 2.)
 constexpr int kTailU = 4;  // slots / rows per thread and pass of the closing write-backs
 template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int RG, int IB, int XW = 0>
-__device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a, const TileShard& sh) {
+__device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a, const TileShard& sh,
+                                                 const TileCall& tc) {
   static_assert((!RG || !XW || XW == 2) && (!IB || XW == 2),
                 "r in global memory not on exchange-wave tiles with workgroup batches; split layouts only with "
                 "wave-local batches");
@@ -1275,9 +1285,12 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
   // r of the local rows as the last call left it; a warm call after a
   // beta_0-only change (capi.hip warm_kinds) starts from r - d B 1, and its
   // own slots' w from w - d (below)
+  // the chains' scalars: the launch's arguments on a one-launch call
+  // (TileCall), else device memory; the shift of the mask's chains only
+  auto scal_of = [&](int ch) -> SweepScalars { return tc.call ? tc.scal[ch] : D.scal[ch]; };
   double dsh[C];
 #pragma unroll
-  for (int ch = 0; ch < C; ++ch) dsh[ch] = D.scal[ch].dshift;
+  for (int ch = 0; ch < C; ++ch) dsh[ch] = ((a.chain_mask >> ch) & 1) ? scal_of(ch).dshift : 0.0;
   for (int lr = t; lr < nrows; lr += NT) {
     const int row = D.erow[row0 + lr];
     const size_t g = (size_t)row * C;
@@ -1295,14 +1308,18 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
     S.gsp_s[i] = D.gslot_ptr[T * K + i];
     if (IB) S.bsp_s[i] = i < K ? D.batch_split[T * K + i] - b_lo : 0;
   }
-  if (t < C) {
-    S.dsh_s[t] = D.scal[t].dshift;
-    S.sc_s[2 * t] = D.scal[t].inv_s2;
-    S.sc_s[2 * t + 1] = D.scal[t].inv_t2;
-    S.seed_s[2 * t] = D.scal[t].seed;
-    S.seed_s[2 * t + 1] = D.scal[t].counter_base;
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    const SweepScalars sc = scal_of(ch);
+    if (t == ch) {
+      S.dsh_s[ch] = dsh[ch];
+      S.sc_s[2 * ch] = sc.inv_s2;
+      S.sc_s[2 * ch + 1] = sc.inv_t2;
+      S.seed_s[2 * ch] = sc.seed;
+      S.seed_s[2 * ch + 1] = sc.counter_base;
+    }
   }
-  S.call = SH ? *sh.call : D.ctl[0];
+  S.call = SH ? *sh.call : (tc.call ? tc.call : D.ctl[0]);
   S.gsl = 0;
   S.tmo = D.ctl + 1;
   S.gran = __builtin_amdgcn_make_buffer_rsrc(SH ? sh.gx[rk] : D.dwx, 0, 0x7FFFFFFF, 0x00020000);
@@ -1422,7 +1439,7 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {
       fld[ch] = a.field.p[ch];
-      b0[ch] = D.scal[ch].beta0;
+      b0[ch] = scal_of(ch).beta0;
     }
     const int x0 = S.batch_s[0].w, x1 = S.batch_s[nbt - 1].w + S.batch_s[nbt - 1].z;
     // kTailU slots per thread and pass: every load of a pass goes out before
@@ -1467,19 +1484,20 @@ __device__ __forceinline__ void sweep_tiles_body(const TileDev& D0, TileLaunch a
 }
 
 template <int C, int NT, int RMAX, int GMAX, int DB, int PROBE, int SH, int RG, int IB, int XW>
-__global__ __launch_bounds__(NT) void sweep_tiles_kernel(TileDev D0, TileLaunch a, TileShard sh) {
-  sweep_tiles_body<C, NT, RMAX, GMAX, DB, PROBE, SH, RG, IB, XW>(D0, a, sh);
+__global__ __launch_bounds__(NT) void sweep_tiles_kernel(TileDev D0, TileLaunch a, TileShard sh, TileCall tc) {
+  sweep_tiles_body<C, NT, RMAX, GMAX, DB, PROBE, SH, RG, IB, XW>(D0, a, sh, tc);
 }
 #undef TSTAMP
 
-// sh == nullptr: one GPU, the call-id bump and the whole grid of tiles here;
+// sh == nullptr: one GPU, the call-id bump (unless the id is an argument,
+// TileCall) and the whole grid of tiles here;
 // else the caller bumped the call ids and `grid` tiles from sh->tile0 run
 // occ != nullptr: no launch -- *occ = the workgroups of exactly this
 // instantiation (and LDS) that fit one CU at once (the residency check of
 // the persistent launch: every tile must be resident, tiles spin on each other)
 template <int C, int NT, int PROBE, int SH, int RG = 0, int IB0 = -1>
 static hipError_t launch_tiles_c(hipStream_t st, const TileDev& D, const TileLaunch& a, int lds, const TileShard* sh,
-                                 int grid, int* occ = nullptr) {
+                                 int grid, int* occ, const TileCall& tc) {
   constexpr int RMAX = tile_rmax(C, NT);
   constexpr int DB = tile_double_buffer(C, NT);
   constexpr int GMAX = tile_gmax(NT);
@@ -1487,8 +1505,8 @@ static hipError_t launch_tiles_c(hipStream_t st, const TileDev& D, const TileLau
   // batches only (XW = 2, instantiated below at these NT, RG, PROBE); IB0 >= 0
   // pins it
   if constexpr (IB0 < 0 && DB == 0 && NT == 512 && (!RG || !PROBE)) {
-    if (D.batch_split) return launch_tiles_c<C, NT, PROBE, SH, RG, 1>(st, D, a, lds, sh, grid, occ);
-    return launch_tiles_c<C, NT, PROBE, SH, RG, 0>(st, D, a, lds, sh, grid, occ);
+    if (D.batch_split) return launch_tiles_c<C, NT, PROBE, SH, RG, 1>(st, D, a, lds, sh, grid, occ, tc);
+    return launch_tiles_c<C, NT, PROBE, SH, RG, 0>(st, D, a, lds, sh, grid, occ, tc);
   }
   constexpr int IB = IB0 > 0 ? 1 : 0;
   if (D.batch_split && (!IB || D.xw != 2)) return hipErrorInvalidValue;  // split layout: no other path runs it
@@ -1507,25 +1525,25 @@ static hipError_t launch_tiles_c(hipStream_t st, const TileDev& D, const TileLau
   if (e != hipSuccess) return e;
   if (occ) return hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(k), NT, lds);
   if constexpr (SH) {
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, D, a, *sh);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(NT), lds, st, D, a, *sh, TileCall());
   } else {
-    hipLaunchKernelGGL(tile_call_bump_kernel, dim3(1), dim3(1), 0, st, D.ctl);
-    hipLaunchKernelGGL(k, dim3(D.T), dim3(NT), lds, st, D, a, TileShard());
+    if (!tc.call) hipLaunchKernelGGL(tile_call_bump_kernel, dim3(1), dim3(1), 0, st, D.ctl);
+    hipLaunchKernelGGL(k, dim3(D.T), dim3(NT), lds, st, D, a, TileShard(), tc);
   }
   return hipGetLastError();
 }
 
 template <int NT>
 static hipError_t launch_tiles_nt(hipStream_t st, const TileDev& D, const TileLaunch& a, int lds, const TileShard* sh,
-                                  int grid, int* occ) {
+                                  int grid, int* occ, const TileCall& tc) {
   if (D.rg) {  // r in global memory: 512- or 1024-thread tiles; tile shards 512
     if constexpr (NT == 512) {
       if (sh) {
         switch (D.C) {
-          case 1: return launch_tiles_c<1, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ);
-          case 2: return launch_tiles_c<2, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ);
-          case 3: return launch_tiles_c<3, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ);
-          case 4: return launch_tiles_c<4, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ);
+          case 1: return launch_tiles_c<1, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ, tc);
+          case 2: return launch_tiles_c<2, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ, tc);
+          case 3: return launch_tiles_c<3, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ, tc);
+          case 4: return launch_tiles_c<4, NT, 0, 1, 1>(st, D, a, lds, sh, grid, occ, tc);
           default: return hipErrorInvalidValue;
         }
       }
@@ -1533,10 +1551,10 @@ static hipError_t launch_tiles_nt(hipStream_t st, const TileDev& D, const TileLa
     if constexpr (NT == 512 || NT == 1024) {
       if (sh) return hipErrorInvalidValue;
       switch (D.C) {
-        case 1: return launch_tiles_c<1, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ);
-        case 2: return launch_tiles_c<2, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ);
-        case 3: return launch_tiles_c<3, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ);
-        case 4: return launch_tiles_c<4, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ);
+        case 1: return launch_tiles_c<1, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ, tc);
+        case 2: return launch_tiles_c<2, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ, tc);
+        case 3: return launch_tiles_c<3, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ, tc);
+        case 4: return launch_tiles_c<4, NT, 0, 0, 1>(st, D, a, lds, nullptr, 0, occ, tc);
         default: return hipErrorInvalidValue;
       }
     }
@@ -1544,43 +1562,45 @@ static hipError_t launch_tiles_nt(hipStream_t st, const TileDev& D, const TileLa
   }
   if (sh) {
     switch (D.C) {
-      case 1: return launch_tiles_c<1, NT, 0, 1>(st, D, a, lds, sh, grid, occ);
-      case 2: return launch_tiles_c<2, NT, 0, 1>(st, D, a, lds, sh, grid, occ);
-      case 3: return launch_tiles_c<3, NT, 0, 1>(st, D, a, lds, sh, grid, occ);
-      case 4: return launch_tiles_c<4, NT, 0, 1>(st, D, a, lds, sh, grid, occ);
+      case 1: return launch_tiles_c<1, NT, 0, 1>(st, D, a, lds, sh, grid, occ, tc);
+      case 2: return launch_tiles_c<2, NT, 0, 1>(st, D, a, lds, sh, grid, occ, tc);
+      case 3: return launch_tiles_c<3, NT, 0, 1>(st, D, a, lds, sh, grid, occ, tc);
+      case 4: return launch_tiles_c<4, NT, 0, 1>(st, D, a, lds, sh, grid, occ, tc);
       default: return hipErrorInvalidValue;
     }
   }
   if (D.dbg && D.probe == 1) {
     switch (D.C) {
-      case 1: return launch_tiles_c<1, NT, 1, 0>(st, D, a, lds, nullptr, 0, occ);
-      case 3: return launch_tiles_c<3, NT, 1, 0>(st, D, a, lds, nullptr, 0, occ);
+      case 1: return launch_tiles_c<1, NT, 1, 0>(st, D, a, lds, nullptr, 0, occ, tc);
+      case 3: return launch_tiles_c<3, NT, 1, 0>(st, D, a, lds, nullptr, 0, occ, tc);
       default: break;
     }
   }
   if (D.dbg && D.probe == 2) {
     switch (D.C) {
-      case 1: return launch_tiles_c<1, NT, 2, 0>(st, D, a, lds, nullptr, 0, occ);
-      case 3: return launch_tiles_c<3, NT, 2, 0>(st, D, a, lds, nullptr, 0, occ);
+      case 1: return launch_tiles_c<1, NT, 2, 0>(st, D, a, lds, nullptr, 0, occ, tc);
+      case 3: return launch_tiles_c<3, NT, 2, 0>(st, D, a, lds, nullptr, 0, occ, tc);
       default: break;
     }
   }
   switch (D.C) {
-    case 1: return launch_tiles_c<1, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ);
-    case 2: return launch_tiles_c<2, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ);
-    case 3: return launch_tiles_c<3, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ);
-    case 4: return launch_tiles_c<4, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ);
+    case 1: return launch_tiles_c<1, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ, tc);
+    case 2: return launch_tiles_c<2, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ, tc);
+    case 3: return launch_tiles_c<3, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ, tc);
+    case 4: return launch_tiles_c<4, NT, 0, 0>(st, D, a, lds, nullptr, 0, occ, tc);
     default: return hipErrorInvalidValue;
   }
 }
 
 hipError_t launch_sweep_tiles(hipStream_t st, const TileDev& D, const TileLaunch& a, int max_rows, int NT,
-                              int max_batches, int max_gslots, const TileShard* sh, int grid, int* occ) {
+                              int max_batches, int max_gslots, const TileShard* sh, int grid, int* occ,
+                              const TileCall* call) {
+  const TileCall tc = call ? *call : TileCall();
   const int lds = tile_lds_bytes(D.rg ? 0 : max_rows, D.C, NT, D.K, max_batches, max_gslots);
   switch (NT) {
-    case 256: return launch_tiles_nt<256>(st, D, a, lds, sh, grid, occ);
-    case 512: return launch_tiles_nt<512>(st, D, a, lds, sh, grid, occ);
-    case 1024: return launch_tiles_nt<1024>(st, D, a, lds, sh, grid, occ);
+    case 256: return launch_tiles_nt<256>(st, D, a, lds, sh, grid, occ, tc);
+    case 512: return launch_tiles_nt<512>(st, D, a, lds, sh, grid, occ, tc);
+    case 1024: return launch_tiles_nt<1024>(st, D, a, lds, sh, grid, occ, tc);
     default: return hipErrorInvalidValue;
   }
 }
