@@ -14,11 +14,12 @@ from .update_gaussian import mcmc_nngp_update_Gaussian, ll_compressed_sparse_cho
 from .run import mcmc_nngp_run  # noqa: F401
 from .estimate import mcmc_nngp_estimate, get_summary  # noqa: F401
 from .predict import mcmc_nngp_predict_field, mcmc_nngp_predict_fixed_effects  # noqa: F401
-from .diagnose import Gelman_Rubin_Brooks, ESS  # noqa: F401
+from .diagnose import Gelman_Rubin_Brooks, ESS, Field_diagnostics, field_diagnostics  # noqa: F401
 
 __all__ = [
     "mcmc_nngp_initialize", "mcmc_nngp_run", "mcmc_nngp_update_Gaussian",
     "mcmc_nngp_estimate", "mcmc_nngp_predict_field", "mcmc_nngp_predict_fixed_effects",
     "ll_compressed_sparse_chol", "ChainContext", "find_ordered_nn", "naive_greedy_coloring",
     "order_maxmin", "Gelman_Rubin_Brooks", "ESS", "get_summary",
+    "Field_diagnostics", "field_diagnostics",
 ]

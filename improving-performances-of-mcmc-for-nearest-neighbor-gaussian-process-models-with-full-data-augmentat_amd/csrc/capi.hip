@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "rec_stream.h"
 #include "summary.h"
+#include "field_diag_run.h"
 #include "predict.h"
 #include "regress.h"
 
@@ -306,6 +307,7 @@ constexpr int kTileTarget = 2048;  // locations per tile (default tile count: n 
 
 thread_local std::string g_err;
 thread_local SummaryStats g_summary_stats;  // of this thread's last successful nngp_summary
+thread_local FieldDiagStats g_field_diag_stats;  // of this thread's last successful nngp_field_diag
 thread_local PredictStats g_predict_stats;  // of this thread's last successful nngp_predict_field
 
 int fail_hip(nngp_ctx* c, hipError_t e, const char* what) {
@@ -3268,6 +3270,25 @@ int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_byt
   if (kernel_ms) *kernel_ms = g_summary_stats.kernel_ms;
   if (staged_bytes) *staged_bytes = g_summary_stats.staged_bytes;
   if (chunk_cols) *chunk_cols = g_summary_stats.chunk_cols;
+  return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- field diagnostics
+int nngp_field_diag(int device, const double* const* blocks, int n_chains, long long rows, long long n,
+                    const double* row_offset, int chunk_cols, double* out, int* order) {
+  std::string err;
+  const int st = field_diag_run(device, blocks, n_chains, rows, n, row_offset, chunk_cols, out, order,
+                                &g_field_diag_stats, err);
+  return st == NNGP_OK ? NNGP_OK : fail_msg(nullptr, st, err);
+}
+
+int nngp_field_diag_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols) {
+  if (g_field_diag_stats.n_chunks < 1)
+    return fail_msg(nullptr, NNGP_ERR_STATE, "field_diag_stats: no field_diag on this thread yet");
+  if (copy_ms) *copy_ms = g_field_diag_stats.copy_ms;
+  if (kernel_ms) *kernel_ms = g_field_diag_stats.kernel_ms;
+  if (staged_bytes) *staged_bytes = g_field_diag_stats.staged_bytes;
+  if (chunk_cols) *chunk_cols = g_field_diag_stats.chunk_cols;
   return NNGP_OK;
 }
 

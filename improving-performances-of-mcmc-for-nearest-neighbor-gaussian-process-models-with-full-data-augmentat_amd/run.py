@@ -6,14 +6,20 @@ import time
 
 import numpy as np
 
-from .diagnose import ESS, Gelman_Rubin_Brooks
+from .diagnose import ESS, Field_diagnostics, Gelman_Rubin_Brooks
 from .update_gaussian import mcmc_nngp_update_Gaussian
 
 
 def mcmc_nngp_run(mcmc_nngp_list, Gelman_Rubin_Brooks_stop=(1.1, 1.1), burn_in=0.5, n_cores=None,
                   field_thinning=1.0, n_iterations_update=200, ancillary=True, n_chromatic=10,
                   save_name=None, n_cycles=1, plot_beta=False, verbose=True, on_chol_error="error",
-                  regression="host"):
+                  regression="host", field_diagnostics=None):
+    """``field_diagnostics``: None (default: nothing), "host" or "hip" appends
+    the digest of Field_diagnostics (per-location R-hat and ess of the field,
+    "hip": on the current device) to diagnostics["field"] each cycle; the stop rule
+    does not read it."""
+    if field_diagnostics not in (None, "host", "hip"):
+        raise ValueError(f"mcmc_nngp_run: field_diagnostics must be None, 'host' or 'hip', not {field_diagnostics!r}")
     L = mcmc_nngp_list
     cycle = 1
     while cycle <= n_cycles:
@@ -46,6 +52,12 @@ def mcmc_nngp_run(mcmc_nngp_list, Gelman_Rubin_Brooks_stop=(1.1, 1.1), burn_in=0
         if verbose:
             print("Gelman-Rubin-Brooks R-hat : ")
             print(dict(zip(grb["names"], np.round(grb["R_hat"], 4))))
+        if field_diagnostics is not None:
+            fd = Field_diagnostics(L, burn_in, backend=field_diagnostics)["digest"]
+            L["diagnostics"].setdefault("field", []).append(fd)
+            if verbose:
+                print("Field R-hat / ess per location : ")
+                print({k: round(v, 4) if isinstance(v, float) else v for k, v in fd.items()})
         rh = grb["R_hat"]
         if rh[0] < Gelman_Rubin_Brooks_stop[0] or np.all(rh[1:] < Gelman_Rubin_Brooks_stop[1]):
             break

@@ -40,6 +40,8 @@
  *   nngp_records_stream ...... records$field in host memory while the chain runs (same lines)
  *   nngp_summary ............. get_summary, Scripts/mcmc_nngp_estimate.R:1-6 (res$field,
  *                              estimate.R:88-94; predicted_field_summary, predict.R:57-58)
+ *   nngp_field_diag .......... Individual_PSRF of Gelman_Rubin_Brooks and ESS,
+ *                              Scripts/mcmc_nngp_diagnose.R:1-24,107-118, per field location
  *   nngp_predict_field ....... the per-sample body of mcmc_nngp_predict_field,
  *                              Scripts/mcmc_nngp_predict.R:39-53, for all samples of a chain
  *   nngp_design_set .......... X, X$locs and beta_interweaved_* kept for the call,
@@ -62,7 +64,7 @@
 extern "C" {
 #endif
 
-#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
+#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats, nngp_field_diag, nngp_field_diag_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
 #define NNGP_SHARD_ID_BYTES 128 /* RCCL unique id */
 #define NNGP_IPC_HANDLE_BYTES 192 /* HIP IPC handles of a tile shard's granule buffer, w replica, flags */
 
@@ -428,6 +430,40 @@ int nngp_summary(int device, const double* const* blocks, const long long* block
  * call (its streams and events are gone when it returns), and
  * scripts/summary_time.py, the R wrapper and a C client all read them here. */
 int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols);
+
+/* ---------- convergence diagnostics per field location (no context) ---------- */
+/* Individual_PSRF of Gelman_Rubin_Brooks and ESS (Scripts/mcmc_nngp_diagnose.R:1-24,
+ * 107-118) of every column of n_chains host blocks; block k is chain k, rows x n
+ * row-major with row pitch n (the saved field rows after burn-in).  row_offset
+ * (n_chains x rows entries in stack order, or NULL) is subtracted from each row.
+ * out: n x 5 column-major (columns R_hat, ess, ess_min, W, Bv); order (n_chains x
+ * n, order[k * n + j], or NULL): the AR order selected for chain k at location j.
+ * Per chain and column (S = rows values x): mean = sum in row order / S; var =
+ * two-pass variance with divisor S - 1; for S < 4 or a centred sum of squares
+ * of exactly 0, ess_k = S and order 0; otherwise P = min(S - 1, int(10 log10 S)),
+ * acf[l] = sum_t xc[t] xc[t+l] / S (l = 0..P), Levinson-Durbin (left at the
+ * first v <= 0), AIC = S log v + 2 l, the first minimum from l = 0 upward,
+ * spec0 = v / (1 - sum phi)^2 and ess_k = S acf[0] / spec0 (S unless spec0 > 0).
+ * Per location: W = mean of the chains' var, Bv = variance of their means with
+ * divisor n_chains - 1 (NaN for one chain),
+ *   R_hat = ((m+1)/m) ((S-1)/S) (Bv/W) + (S+1)/S     (m = n_chains)
+ * in plain IEEE division (0/0 = NaN, x/0 = inf), ess = sum of ess_k, ess_min
+ * their minimum.  A column holding a NaN in any chain gives five NaNs and
+ * order 0.  A location's numbers depend on its column alone: not on n, the
+ * chunking or the column's position.
+ * Staging as nngp_summary: the blocks are read where they lie, column chunks go
+ * through two device buffers, the copy of one chunk running beside the kernel
+ * of the chunk before; chunk_cols: 0 = automatic (both buffers within 1 GiB,
+ * never below 64 columns), else the columns staged per launch.  device: HIP
+ * ordinal (-1: current); the calling thread's current device is the same after
+ * the call as before it.  NNGP_ERR_ARG (before any HIP call): a null block,
+ * n < 1, n_chains outside 1..16, rows outside 2..9999, chunk_cols < 0. */
+int nngp_field_diag(int device, const double* const* blocks, int n_chains, long long rows,
+                    long long n, const double* row_offset, int chunk_cols,
+                    double* out, int* order);
+/* Measurement, as nngp_summary_stats: the calling thread's last successful
+ * nngp_field_diag.  Any pointer may be NULL.  NNGP_ERR_STATE: none yet. */
+int nngp_field_diag_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols);
 
 /* ---------- posterior prediction at new locations (no context) ---------- */
 /* The samples of mcmc_nngp_predict_field (Scripts/mcmc_nngp_predict.R:39-53) for

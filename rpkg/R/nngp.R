@@ -105,6 +105,17 @@ nngp_get_summary <- function(samples, device = -1L) {
 }
 # HIP-event times (ms), staged bytes and chunk width of the last nngp_get_summary
 nngp_summary_stats <- function() .Call(C_nngp_summary_stats)
+# R-hat (Individual_PSRF of Gelman_Rubin_Brooks, n := saved rows) and effective sample size (ESS) of every
+# field location (Scripts/mcmc_nngp_diagnose.R:1-24,107-118) on the device.  chains: a list with one
+# samples x locations matrix per chain (the saved field rows after burn-in, centred); -> n x 5 with
+# columns R_hat, ess, ess_min, W, Bv
+nngp_field_diagnostics <- function(chains, device = -1L) {
+  if (is.matrix(chains)) chains <- list(chains)
+  chains_t <- lapply(chains, function(x) { x <- t(x); storage.mode(x) <- "double"; x })
+  .Call(C_nngp_field_diag, as.integer(device), chains_t)
+}
+# HIP-event times (ms), staged bytes and chunk width of the last nngp_field_diagnostics
+nngp_field_diag_stats <- function() .Call(C_nngp_field_diag_stats)
 # The predicted samples (n_samples x n_pred) of one chain in one call (Scripts/mcmc_nngp_predict.R:39-53):
 # locs / NNarray of the stacked locations (the n observed first), covparms one row per distinct factor,
 # factor_of (1-based row of covparms per sample), fields n_samples x n (the chain's saved fields of the

@@ -484,6 +484,59 @@ SEXP C_nngp_summary_stats(void) {
   return out;
 }
 
+/* Per-location R-hat and effective sample size of the field samples
+ * (Scripts/mcmc_nngp_diagnose.R:1-24,107-118).  chains_t: a list with one
+ * n x S numeric matrix per chain, the TRANSPOSE of its S saved rows x n
+ * locations, so that R's column-major storage is the S row-major rows of n the
+ * library reads where they lie; -> n x 5 with named columns. */
+SEXP C_nngp_field_diag(SEXP device, SEXP chains_t) {
+  if (TYPEOF(chains_t) != VECSXP || XLENGTH(chains_t) < 1 || XLENGTH(chains_t) > 16)
+    Rf_error("nngp: chains must be a list of 1 to 16 numeric matrices");
+  const int m = (int)XLENGTH(chains_t);
+  const double* blocks[16];
+  int n = 0, S = 0;
+  for (int k = 0; k < m; ++k) {
+    SEXP x = VECTOR_ELT(chains_t, k);
+    if (TYPEOF(x) != REALSXP || !Rf_isMatrix(x)) Rf_error("nngp: every chain must be a numeric matrix");
+    if (k == 0) {
+      n = Rf_nrows(x);
+      S = Rf_ncols(x);
+    } else if (Rf_nrows(x) != n || Rf_ncols(x) != S) {
+      Rf_error("nngp: the chains' matrices must have one shape");
+    }
+    blocks[k] = REAL(x);
+  }
+  static const char* names[5] = {"R_hat", "ess", "ess_min", "W", "Bv"};
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n, 5));
+  check(nngp_field_diag(as_int(device), blocks, m, S, n, NULL, 0, REAL(out), NULL), NULL);
+  SEXP cn = PROTECT(Rf_allocVector(STRSXP, 5));
+  for (int i = 0; i < 5; ++i) SET_STRING_ELT(cn, i, Rf_mkChar(names[i]));
+  SEXP dn = PROTECT(Rf_allocVector(VECSXP, 2));
+  SET_VECTOR_ELT(dn, 1, cn);
+  Rf_setAttrib(out, Rf_install("dimnames"), dn);
+  UNPROTECT(3);
+  return out;
+}
+
+/* the last field diagnostics' HIP-event times (ms), staged bytes and chunk width */
+SEXP C_nngp_field_diag_stats(void) {
+  static const char* names[4] = {"copy_ms", "kernel_ms", "staged_bytes", "chunk_cols"};
+  double copy_ms = 0, kernel_ms = 0;
+  long long bytes = 0;
+  int cols = 0;
+  check(nngp_field_diag_stats(&copy_ms, &kernel_ms, &bytes, &cols), NULL);
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, 4));
+  SEXP nm = PROTECT(Rf_allocVector(STRSXP, 4));
+  REAL(out)[0] = copy_ms;
+  REAL(out)[1] = kernel_ms;
+  REAL(out)[2] = (double)bytes;
+  REAL(out)[3] = (double)cols;
+  for (int i = 0; i < 4; ++i) SET_STRING_ELT(nm, i, Rf_mkChar(names[i]));
+  Rf_setAttrib(out, R_NamesSymbol, nm);
+  UNPROTECT(2);
+  return out;
+}
+
 /* nngp_predict_field for one chain (Scripts/mcmc_nngp_predict.R:39-53 for all of
  * its saved samples).  locs N x d and NNarray N x b as R holds them.  The
  * per-sample matrices come TRANSPOSED from the R side, so that R's column-major
@@ -902,6 +955,8 @@ static const R_CallMethodDef call_methods[] = {
     E(C_nngp_device_normals, 4),
     E(C_nngp_summary, 2),
     E(C_nngp_summary_stats, 0),
+    E(C_nngp_field_diag, 2),
+    E(C_nngp_field_diag_stats, 0),
     E(C_nngp_predict_field, 14),
     E(C_nngp_predict_stats, 0),
     E(C_nngp_get_sweep_r, 1),
