@@ -306,7 +306,7 @@ constexpr int kTileNT = 512;       // threads per tile workgroup (NNGP_TILE_NT: 
 constexpr int kTileTarget = 2048;  // locations per tile (default tile count: n / this, <= CUs)
 
 thread_local std::string g_err;
-thread_local SummaryStats g_summary_stats;  // of this thread's last successful nngp_summary
+thread_local SummaryStats g_summary_stats;  // of this thread's last successful nngp_summary / nngp_summary_probs
 thread_local FieldDiagStats g_field_diag_stats;  // of this thread's last successful nngp_field_diag
 thread_local PredictStats g_predict_stats;  // of this thread's last successful nngp_predict_field
 
@@ -3261,6 +3261,15 @@ int nngp_summary(int device, const double* const* blocks, const long long* block
                  const double* row_offset, int chunk_cols, double* out) {
   std::string err;
   const int st = summary_run(device, blocks, block_rows, n_blocks, n, row_offset, chunk_cols, out, &g_summary_stats, err);
+  return st == NNGP_OK ? NNGP_OK : fail_msg(nullptr, st, err);
+}
+
+int nngp_summary_probs(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
+                       const double* row_offset, int chunk_cols, const double* probs, int n_probs,
+                       const double* thresholds, int n_thresholds, double* out) {
+  std::string err;
+  const int st = summary_run_probs(device, blocks, block_rows, n_blocks, n, row_offset, chunk_cols, probs, n_probs,
+                                   thresholds, n_thresholds, out, &g_summary_stats, err);
   return st == NNGP_OK ? NNGP_OK : fail_msg(nullptr, st, err);
 }
 

@@ -1,5 +1,7 @@
 // get_summary on the device (Scripts/mcmc_nngp_estimate.R:1-6): mean, three
-// type-7 quantiles and sd of every column of a samples x locations matrix.
+// type-7 quantiles and sd of every column of a samples x locations matrix
+// (nngp_summary), or mean, the quantiles asked for, sd and the exceedance
+// fractions P(x > t) (nngp_summary_probs).
 //
 // One lane owns one column of a staged chunk (S rows x w columns, row-major,
 // pitch W): in every pass a wavefront reads 64 neighbouring columns of a row,
@@ -50,11 +52,43 @@ __global__ __launch_bounds__(kSummaryBlock) void summary_kernel(const double* __
   for (int q = 0; q < kSummaryCols; ++q) out[q * n + c0 + c] = r[q];
 }
 
+// The request of nngp_summary_probs, a kernel argument: the same for every
+// lane, so the probabilities and thresholds are scalar loads.
+struct SummaryRequest {
+  double probs[kSummaryProbsMax];
+  double thr[kSummaryThrMax];
+  int n_probs, n_thr;
+};
+
+// out: n x (2 + n_probs + n_thr) column-major; columns c0 .. c0 + w - 1.
+// With row offsets the kernel is held to 4 waves per SIMD (110 VGPRs instead
+// of 132 at 4-bit digits, no scratch; measured ahead); without
+// them that bound would spill, so it is left to the compiler (144 VGPRs).
+template <int BITS, bool OFF>
+__global__ __launch_bounds__(kSummaryBlock, OFF ? 4 : 1) void summary_probs_kernel(const double* __restrict__ x,
+                                                                      const double* __restrict__ off, long long S, int w,
+                                                                      long long pitch, const SummaryRequest req,
+                                                                      double* __restrict__ out, long long n, long long c0) {
+  const int c = blockIdx.x * kSummaryBlock + threadIdx.x;
+  if (c >= w) return;
+  if constexpr (OFF)
+    summary_column_probs<BITS>(ColumnLoad{x + c, off, pitch}, S, req.probs, req.n_probs, req.thr, req.n_thr,
+                               out + c0 + c, n);
+  else
+    summary_column_probs<BITS>(ColumnLoadPlain{x + c, pitch}, S, req.probs, req.n_probs, req.thr, req.n_thr,
+                               out + c0 + c, n);
+}
+
+// req == nullptr: the five fixed columns of nngp_summary
 template <int BITS>
 hipError_t launch_summary(hipStream_t st, const double* x, const double* off, long long S, int w, long long pitch,
-                          double* out, long long n, long long c0) {
+                          const SummaryRequest* req, double* out, long long n, long long c0) {
   const dim3 grid((w + kSummaryBlock - 1) / kSummaryBlock), block(kSummaryBlock);
-  if (off)
+  if (req && off)
+    hipLaunchKernelGGL((summary_probs_kernel<BITS, true>), grid, block, 0, st, x, off, S, w, pitch, *req, out, n, c0);
+  else if (req)
+    hipLaunchKernelGGL((summary_probs_kernel<BITS, false>), grid, block, 0, st, x, off, S, w, pitch, *req, out, n, c0);
+  else if (off)
     hipLaunchKernelGGL((summary_kernel<BITS, true>), grid, block, 0, st, x, off, S, w, pitch, out, n, c0);
   else
     hipLaunchKernelGGL((summary_kernel<BITS, false>), grid, block, 0, st, x, off, S, w, pitch, out, n, c0);
@@ -81,10 +115,10 @@ struct SummaryDev {
   }
 };
 
-}  // namespace
-
-int summary_run(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
-                const double* row_offset, int chunk_cols, double* out, SummaryStats* stats, std::string& err) {
+// The one staging loop of both entry points; out: n x ncols column-major.
+int summary_stage(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
+                  const double* row_offset, int chunk_cols, const SummaryRequest* req, int ncols, double* out,
+                  SummaryStats* stats, std::string& err) {
   if (!blocks || !block_rows || !out || n_blocks < 1 || n < 1 || chunk_cols < 0) {
     err = "summary: bad args";
     return NNGP_ERR_ARG;
@@ -156,7 +190,7 @@ int summary_run(int device, const double* const* blocks, const long long* block_
       err = "summary: staging buffers do not fit the device (smaller chunk_cols?)";
       return NNGP_ERR_NOMEM;
     }
-  if (hipMalloc((void**)&D.out, sizeof(double) * kSummaryCols * (size_t)n) != hipSuccess ||
+  if (hipMalloc((void**)&D.out, sizeof(double) * (size_t)ncols * (size_t)n) != hipSuccess ||
       (row_offset && hipMalloc((void**)&D.off, sizeof(double) * (size_t)S) != hipSuccess)) {
     (void)hipGetLastError();
     err = "summary: device allocation failed";
@@ -211,18 +245,58 @@ int summary_run(int device, const double* const* blocks, const long long* block_
     SUMMARY_HIP(hipStreamWaitEvent(D.run_st, D.copy1[b], 0));
     SUMMARY_HIP(hipEventRecord(D.run0[b], D.run_st));
     if (bits == 4)
-      SUMMARY_HIP(launch_summary<4>(D.run_st, D.buf[b], D.off, S, w, W, D.out, n, c0));
+      SUMMARY_HIP(launch_summary<4>(D.run_st, D.buf[b], D.off, S, w, W, req, D.out, n, c0));
     else
-      SUMMARY_HIP(launch_summary<2>(D.run_st, D.buf[b], D.off, S, w, W, D.out, n, c0));
+      SUMMARY_HIP(launch_summary<2>(D.run_st, D.buf[b], D.off, S, w, W, req, D.out, n, c0));
     SUMMARY_HIP(hipEventRecord(D.run1[b], D.run_st));
   }
   st.n_chunks = (int)k;
-  SUMMARY_HIP(hipMemcpyAsync(out, D.out, sizeof(double) * kSummaryCols * (size_t)n, hipMemcpyDeviceToHost, D.run_st));
+  SUMMARY_HIP(hipMemcpyAsync(out, D.out, sizeof(double) * (size_t)ncols * (size_t)n, hipMemcpyDeviceToHost, D.run_st));
   SUMMARY_HIP(hipStreamSynchronize(D.run_st));
   for (long long q = std::max(0LL, k - 2); q < k; ++q) SUMMARY_HIP(collect((int)(q & 1)));
 #undef SUMMARY_HIP
   if (stats) *stats = st;
   return NNGP_OK;
+}
+
+}  // namespace
+
+int summary_run(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
+                const double* row_offset, int chunk_cols, double* out, SummaryStats* stats, std::string& err) {
+  return summary_stage(device, blocks, block_rows, n_blocks, n, row_offset, chunk_cols, nullptr, kSummaryCols, out, stats,
+                       err);
+}
+
+int summary_run_probs(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
+                      const double* row_offset, int chunk_cols, const double* probs, int n_probs,
+                      const double* thresholds, int n_thresholds, double* out, SummaryStats* stats, std::string& err) {
+  if (n_probs < 0 || n_probs > kSummaryProbsMax || n_thresholds < 0 || n_thresholds > kSummaryThrMax) {
+    err = "summary: n_probs must be 0..16 and n_thresholds 0..8";
+    return NNGP_ERR_ARG;
+  }
+  if ((n_probs > 0 && !probs) || (n_thresholds > 0 && !thresholds)) {
+    err = "summary: null probs or thresholds with a positive count";
+    return NNGP_ERR_ARG;
+  }
+  SummaryRequest req = {};
+  req.n_probs = n_probs;
+  req.n_thr = n_thresholds;
+  for (int i = 0; i < n_probs; ++i) {
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) {  // a NaN fails both compares
+      err = "summary: a probability is NaN or outside [0, 1]";
+      return NNGP_ERR_ARG;
+    }
+    req.probs[i] = probs[i];
+  }
+  for (int k = 0; k < n_thresholds; ++k) {
+    if (thresholds[k] != thresholds[k]) {
+      err = "summary: a threshold is NaN";
+      return NNGP_ERR_ARG;
+    }
+    req.thr[k] = thresholds[k];
+  }
+  return summary_stage(device, blocks, block_rows, n_blocks, n, row_offset, chunk_cols, &req, 2 + n_probs + n_thresholds,
+                       out, stats, err);
 }
 
 }  // namespace nngp

@@ -1,9 +1,11 @@
 // Per-column posterior summary (get_summary, Scripts/mcmc_nngp_estimate.R:1-6):
 // mean, the type-7 quantiles 0.025 / 0.5 / 0.975 and sd of S values that are
 // only ever streamed -- nothing here holds a column, so S is bounded by the
-// 32-bit counters (S < 2^31), not by registers or LDS.  __host__ __device__:
-// summary.hip runs it with one lane per column, tests/cpp/summary_select_check.cpp
-// compiles the same text for the CPU.
+// 32-bit counters (S < 2^31), not by registers or LDS.  summary_column_probs
+// is the same with the quantiles chosen by the caller and exceedance
+// fractions.  __host__ __device__: summary.hip runs it with one lane per
+// column, tests/cpp/summary_select_check.cpp and summary_probs_check.cpp
+// compile the same text for the CPU.
 //
 // A column is a functor `double load(long long s)`, s = 0..S-1; every pass
 // calls it for all s in increasing order.
@@ -170,6 +172,85 @@ NNGP_HD void summary_column(Load load, long long S, double* out) {
 #pragma unroll
   for (int r = 0; r < kSummaryQ; ++r) out[1 + r] = nan ? qnan : summary_lerp(lo[r], hi[r], g[r]);
   out[4] = (nan || S < 2) ? qnan : sqrt(ss / (double)(S - 1));
+}
+
+constexpr int kSummaryProbsMax = 16;  // quantiles per request
+constexpr int kSummaryThrMax = 8;     // exceedance thresholds per request
+
+// The general column summary: out[0] = mean, out[(1 + i) stride] = the type-7
+// quantile probs[i] (i < n_probs <= kSummaryProbsMax, in [0, 1], any order,
+// repeats allowed; 0 and 1 are the exact minimum and maximum),
+// out[(1 + n_probs) stride] = sd, out[(2 + n_probs + k) stride] =
+// count(x > thr[k]) / S (k < n_thr <= kSummaryThrMax; strict compare, integer
+// count, one division).  Mean, sd, ranks and interpolation are
+// summary_column's, so probs = (0.025, 0.5, 0.975) without thresholds gives
+// its five numbers bit for bit.  A column that holds a NaN gives NaNs only.
+//
+// The ranks go through summary_select in rounds of kSummaryQ (a short last
+// round repeats its first rank): the counters of a round are the existing
+// 3 x 2^BITS registers, and the select is exact, so a quantile's bits depend
+// on its column and its own q only -- not on the round it fell into, the
+// other probabilities or the thresholds.  The exceedance counts ride on the
+// mean pass: kSummaryThrMax statically indexed counters, the unused ones
+// compared against +inf (never exceeded).  Results are stored as they are
+// found; nothing here is indexed by a run-time value except probs and thr,
+// which the kernel holds in scalar memory.
+template <int BITS, class Load>
+NNGP_HD void summary_column_probs(Load load, long long S, const double* probs, int n_probs, const double* thr,
+                                  int n_thr, double* out, long long stride) {
+#pragma clang fp contract(off)
+  double sum = 0.0;
+  bool nan = false;
+  uint32_t above[kSummaryThrMax];
+#pragma unroll
+  for (int k = 0; k < kSummaryThrMax; ++k) above[k] = 0;
+  if (n_thr > 0) {
+    double t[kSummaryThrMax];
+#pragma unroll
+    for (int k = 0; k < kSummaryThrMax; ++k) t[k] = k < n_thr ? thr[k] : std::numeric_limits<double>::infinity();
+#pragma unroll 4
+    for (long long s = 0; s < S; ++s) {
+      const double x = load(s);
+      nan = nan || x != x;
+      sum += x;
+#pragma unroll
+      for (int k = 0; k < kSummaryThrMax; ++k) above[k] += x > t[k];
+    }
+  } else {
+#pragma unroll 4
+    for (long long s = 0; s < S; ++s) {
+      const double x = load(s);
+      nan = nan || x != x;
+      sum += x;
+    }
+  }
+  const double mean = sum / (double)S;
+  double ss = 0.0;
+#pragma unroll 4
+  for (long long s = 0; s < S; ++s) {
+    const double d = load(s) - mean;
+    ss += d * d;
+  }
+  const double qnan = std::numeric_limits<double>::quiet_NaN();
+  out[0] = nan ? qnan : mean;
+  out[(1 + n_probs) * stride] = (nan || S < 2) ? qnan : sqrt(ss / (double)(S - 1));
+#pragma unroll
+  for (int k = 0; k < kSummaryThrMax; ++k)
+    if (k < n_thr) out[(2 + n_probs + k) * stride] = nan ? qnan : (double)above[k] / (double)S;
+  for (int q0 = 0; q0 < n_probs; q0 += kSummaryQ) {
+    long long j[kSummaryQ];
+    double g[kSummaryQ], lo[kSummaryQ], hi[kSummaryQ];
+    bool want_hi = false;
+#pragma unroll
+    for (int r = 0; r < kSummaryQ; ++r) {
+      summary_rank(probs[q0 + r < n_probs ? q0 + r : q0], S, &j[r], &g[r]);
+      want_hi = want_hi || g[r] != 0.0;
+    }
+    summary_select<BITS>(load, S, j, want_hi, lo, hi);
+#pragma unroll
+    for (int r = 0; r < kSummaryQ; ++r)
+      if (q0 + r < n_probs) out[(1 + q0 + r) * stride] = nan ? qnan : summary_lerp(lo[r], hi[r], g[r]);
+  }
 }
 
 }  // namespace nngp

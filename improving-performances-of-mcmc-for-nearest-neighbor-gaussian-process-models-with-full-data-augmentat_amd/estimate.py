@@ -11,7 +11,40 @@ def _quantile7(x, q):
     return np.quantile(x, q, axis=0)  # numpy 'linear' == R type 7
 
 
-def get_summary(samples, backend="host", device=-1, row_offset=None, chunk_cols=0):
+DEFAULT_PROBS = (0.025, 0.5, 0.975)
+MAX_PROBS, MAX_THRESHOLDS = 16, 8  # kSummaryProbsMax, kSummaryThrMax (csrc/summary_select.h)
+
+
+def _summary_request(probs, thresholds):
+    """The checked request of a widened summary: (probs, thresholds) as float64
+    vectors, ``probs=None`` being the default three.  One wording for both
+    backends; the library checks the same again."""
+    p = np.asarray(DEFAULT_PROBS if probs is None else probs, np.float64)
+    t = np.asarray(() if thresholds is None else thresholds, np.float64)
+    if p.ndim > 1 or t.ndim > 1:
+        raise ValueError("get_summary: probs and thresholds must be scalars or 1-D")
+    p, t = np.ascontiguousarray(p.reshape(-1)), np.ascontiguousarray(t.reshape(-1))
+    if p.size > MAX_PROBS:
+        raise ValueError(f"get_summary: at most {MAX_PROBS} probs, not {p.size}")
+    if t.size > MAX_THRESHOLDS:
+        raise ValueError(f"get_summary: at most {MAX_THRESHOLDS} thresholds, not {t.size}")
+    if not np.all((p >= 0.0) & (p <= 1.0)):  # a NaN fails both compares
+        raise ValueError("get_summary: probs must lie in [0, 1]")
+    if np.any(np.isnan(t)):
+        raise ValueError("get_summary: thresholds must not be NaN")
+    return p, t
+
+
+def summary_columns(probs=None, thresholds=None):
+    """The column names of get_summary(..., probs, thresholds): SUMMARY_COLS
+    for the defaults, else mean, q<p>..., sd, p_gt_<t>..."""
+    if probs is None and thresholds is None:
+        return list(SUMMARY_COLS)
+    p, t = _summary_request(probs, thresholds)
+    return ["mean"] + [f"q{v:g}" for v in p] + ["sd"] + [f"p_gt_{v:g}" for v in t]
+
+
+def get_summary(samples, backend="host", device=-1, row_offset=None, chunk_cols=0, probs=None, thresholds=None):
     """estimate.R:1-6: mean, q0.025, median, q0.975, sd per column.
 
     ``samples``: a 2-D array (rows = samples) or a list of 2-D arrays with equal
@@ -21,9 +54,19 @@ def get_summary(samples, backend="host", device=-1, row_offset=None, chunk_cols=
     kernel of libnngp.so (nngp_summary) on ``device``: float64 row-contiguous
     blocks are passed where they lie, any other block is copied (only that
     block), and ``chunk_cols`` columns are staged per launch (0: automatic).
-    Returns an (n, 5) array."""
+    Returns an (n, 5) array.
+
+    ``probs`` (up to 16 probabilities in [0, 1], any order, repeats allowed)
+    and ``thresholds`` (up to 8 values, +-inf allowed) widen it: with either
+    given the result is (n, 2 + Q + K) with the columns of
+    ``summary_columns(probs, thresholds)`` -- mean, the type-7 quantiles in
+    the order of ``probs`` (None: the default three), sd, then the exceedance
+    fractions P(x > t) = count(x > t) / rows of the values summarised (after
+    ``row_offset``).  The device backend calls nngp_summary_probs; a column
+    holding a NaN gives NaNs on both."""
+    req = None if probs is None and thresholds is None else _summary_request(probs, thresholds)
     if backend == "hip":
-        return _summary_hip(samples, device, row_offset, chunk_cols)
+        return _summary_hip(samples, device, row_offset, chunk_cols, req)
     if backend != "host":
         raise ValueError(f"get_summary: backend must be 'host' or 'hip', not {backend!r}")
     if isinstance(samples, (list, tuple)) and len(samples) and np.ndim(samples[0]) == 2:
@@ -33,11 +76,16 @@ def get_summary(samples, backend="host", device=-1, row_offset=None, chunk_cols=
     s = np.atleast_2d(np.asarray(samples, np.float64))
     if s.shape[0] == 1 and s.ndim == 2 and s.shape[1] > 1 and np.asarray(samples).ndim == 1:
         s = s.T
+    if req is not None:
+        p, t = req
+        bad = np.isnan(s).any(0)
+        above = [np.where(bad, np.nan, (s > v).sum(0) / s.shape[0]) for v in t]
+        return np.column_stack([s.mean(0), *_quantile7(s, p), s.std(0, ddof=1), *above])
     return np.column_stack([s.mean(0), _quantile7(s, 0.025), _quantile7(s, 0.5), _quantile7(s, 0.975),
                             s.std(0, ddof=1)])
 
 
-def _summary_hip(samples, device, row_offset, chunk_cols):
+def _summary_hip(samples, device, row_offset, chunk_cols, req=None):
     import ctypes as C
 
     from . import _lib
@@ -63,6 +111,14 @@ def _summary_hip(samples, device, row_offset, chunk_cols):
         off = _lib.f64(np.asarray(row_offset).reshape(-1))
         if off.size != sum(b.shape[0] for b in blocks):
             raise ValueError("get_summary: row_offset needs one entry per row")
+    if req is not None:
+        p, t = req
+        out = np.empty((2 + p.size + t.size, max(n, 1)))  # n x (2 + Q + K) column-major
+        _lib.check(_lib.lib.nngp_summary_probs(int(device), ptrs, rows, len(blocks), n,
+                                               None if off is None else off.ctypes.data, int(chunk_cols),
+                                               p.ctypes.data if p.size else None, p.size,
+                                               t.ctypes.data if t.size else None, t.size, out))
+        return np.ascontiguousarray(out.T)
     out = np.empty((5, max(n, 1)))  # n x 5 column-major
     _lib.check(_lib.lib.nngp_summary(int(device), ptrs, rows, len(blocks), n, None if off is None else off.ctypes.data,
                                      int(chunk_cols), out))
@@ -85,12 +141,16 @@ def _plogis(x):
     return 1 / (1 + np.exp(-x))
 
 
-def mcmc_nngp_estimate(mcmc_nngp_list, burn_in=0.5, field_backend="host", device=-1):
+def mcmc_nngp_estimate(mcmc_nngp_list, burn_in=0.5, field_backend="host", device=-1, field_probs=None,
+                       field_thresholds=None):
     """estimate.R:9-96.  ``field_backend="hip"`` takes res["field"] (the one
     summary as wide as the field) from the device get_summary on ``device``;
     the covariance and fixed-effect summaries are a handful of columns and
     stay on the host.  A burn_in that leaves no saved field row raises
-    NNGPError (status 1: no rows) there, where the host path returns NaNs."""
+    NNGPError (status 1: no rows) there, where the host path returns NaNs.
+    ``field_probs`` / ``field_thresholds`` are get_summary's ``probs`` /
+    ``thresholds`` for res["field"] (both backends); with either given,
+    res["field_columns"] names its columns."""
     if field_backend not in ("host", "hip"):
         raise ValueError(f"mcmc_nngp_estimate: field_backend must be 'host' or 'hip', not {field_backend!r}")
     L = mcmc_nngp_list
@@ -99,6 +159,10 @@ def mcmc_nngp_estimate(mcmc_nngp_list, burn_in=0.5, field_backend="host", device
     it = int(first["iterations"][-1, 0])
     lo = int(burn_in * it) - 1
     res = {"covariance_params": {}}
+    widen = {}
+    if field_probs is not None or field_thresholds is not None:
+        widen = {"probs": field_probs, "thresholds": field_thresholds}
+        res["field_columns"] = summary_columns(field_probs, field_thresholds)
     sp = L["space_time_model"]["covfun"]["shape_params"]
     names = ["log_scale", "log_noise_variance"] + list(sp)
     samples = np.vstack([np.column_stack([c["params"]["log_scale"], c["params"]["log_noise_variance"],
@@ -169,11 +233,11 @@ def mcmc_nngp_estimate(mcmc_nngp_list, burn_in=0.5, field_backend="host", device
             f = c["params"]["field"]
             fs.append(f[idx[0]:] if suffix and f.shape[0] == sel.size else f[sel])
         offs = np.concatenate([c["params"]["beta_0"][b0_rows, 0] for c in recs.values()])
-        res["field"] = get_summary(fs, backend="hip", device=device, row_offset=offs)
+        res["field"] = get_summary(fs, backend="hip", device=device, row_offset=offs, **widen)
         return res
     for c in recs.values():
         f = c["params"]["field"][sel]
         b0 = c["params"]["beta_0"][saved[sel].astype(int) - 1, 0]
         fs.append(f - b0[:, None])
-    res["field"] = get_summary(np.vstack(fs))
+    res["field"] = get_summary(np.vstack(fs), **widen)
     return res

@@ -19,19 +19,22 @@ import numpy as np
 
 from . import _lib
 from .context import ChainContext
-from .estimate import get_summary
+from .estimate import get_summary, summary_columns
 from .graph import find_ordered_nn, naive_greedy_coloring
 from .model import covparms
 
 
 def mcmc_nngp_predict_field(mcmc_nngp_list, predicted_locs, burn_in=0.5, n_cores=1, m=10, seed=1,
                             device=-1, z_new=None, summary_backend="host", engine="context", rng="numpy",
-                            sample_batch=0):
+                            sample_batch=0, summary_probs=None, summary_thresholds=None):
     """predict.R:1-60.  ``z_new`` (optional) replaces the rnorm draws of the
     new locations (predict.R:50): z_new[k][i] = the normals of chain k's i-th
     prediction; by default they come from numpy's generator seeded ``seed``.
     ``summary_backend="hip"`` summarises the per-chain sample arrays on the
     device (get_summary, no stacked copy); the samples are the same.
+    ``summary_probs`` / ``summary_thresholds`` are get_summary's ``probs`` /
+    ``thresholds`` for predicted_field_summary (both backends, both engines);
+    with either given, predicted_field_summary_columns names its columns.
 
     ``engine="batched"``: one nngp_predict_field call per chain, reading
     chain["params"]["field"] where it lies; no colouring and no ChainContext.
@@ -52,7 +55,7 @@ def mcmc_nngp_predict_field(mcmc_nngp_list, predicted_locs, burn_in=0.5, n_cores
         raise ValueError("mcmc_nngp_predict_field: rng='philox' needs engine='batched'")
     if engine == "batched":
         return _predict_field_batched(mcmc_nngp_list, predicted_locs, burn_in, m, seed, device, z_new,
-                                      summary_backend, rng, sample_batch)
+                                      summary_backend, rng, sample_batch, summary_probs, summary_thresholds)
     L = mcmc_nngp_list
     locs = L["locs"]
     predicted_locs = np.asarray(predicted_locs, np.float64)
@@ -87,10 +90,8 @@ def mcmc_nngp_predict_field(mcmc_nngp_list, predicted_locs, burn_in=0.5, n_cores
             samples[k] = sd * x[n:]
         out.append(samples)
     ctx.close()
-    summary = get_summary(out, backend="hip", device=device) if summary_backend == "hip" \
-        else get_summary(np.vstack(out))
     return {"predicted_locs": predicted_locs, "predicted_field_samples": out,
-            "predicted_field_summary": summary}
+            **_field_summary(out, summary_backend, device, summary_probs, summary_thresholds)}
 
 
 def predict_field_call(locs, NN, n, covfun, covparms_rows, factor_of, fields, field_row, beta0, log_scale,
@@ -153,7 +154,19 @@ def predict_stats():
 PHILOX_CHAIN_MIX = 0x9E3779B97F4A7C15
 
 
-def _predict_field_batched(L, predicted_locs, burn_in, m, seed, device, z_new, summary_backend, rng, sample_batch):
+def _field_summary(out, summary_backend, device, probs, thresholds):
+    """predicted_field_summary (and its column names when it is widened)."""
+    widen = {} if probs is None and thresholds is None else {"probs": probs, "thresholds": thresholds}
+    summary = get_summary(out, backend="hip", device=device, **widen) if summary_backend == "hip" \
+        else get_summary(np.vstack(out), **widen)
+    res = {"predicted_field_summary": summary}
+    if widen:
+        res["predicted_field_summary_columns"] = summary_columns(probs, thresholds)
+    return res
+
+
+def _predict_field_batched(L, predicted_locs, burn_in, m, seed, device, z_new, summary_backend, rng, sample_batch,
+                           summary_probs=None, summary_thresholds=None):
     locs = L["locs"]
     predicted_locs = np.asarray(predicted_locs, np.float64)
     allloc = np.vstack([locs, predicted_locs])
@@ -191,10 +204,8 @@ def _predict_field_batched(L, predicted_locs, burn_in, m, seed, device, z_new, s
                                       chain["params"]["beta_0"][stored - 1, 0],
                                       chain["params"]["log_scale"][stored - 1, 0],
                                       sample_batch=sample_batch, device=device, **kw))
-    summary = get_summary(out, backend="hip", device=device) if summary_backend == "hip" \
-        else get_summary(np.vstack(out))
     return {"predicted_locs": predicted_locs, "predicted_field_samples": out,
-            "predicted_field_summary": summary}
+            **_field_summary(out, summary_backend, device, summary_probs, summary_thresholds)}
 
 
 def mcmc_nngp_predict_fixed_effects(mcmc_nngp_list, X_predicted, burn_in=0.5, n_cores=1,

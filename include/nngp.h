@@ -40,6 +40,7 @@
  *   nngp_records_stream ...... records$field in host memory while the chain runs (same lines)
  *   nngp_summary ............. get_summary, Scripts/mcmc_nngp_estimate.R:1-6 (res$field,
  *                              estimate.R:88-94; predicted_field_summary, predict.R:57-58)
+ *   nngp_summary_probs ....... the same with chosen quantiles and exceedance probabilities
  *   nngp_field_diag .......... Individual_PSRF of Gelman_Rubin_Brooks and ESS,
  *                              Scripts/mcmc_nngp_diagnose.R:1-24,107-118, per field location
  *   nngp_predict_field ....... the per-sample body of mcmc_nngp_predict_field,
@@ -64,7 +65,7 @@
 extern "C" {
 #endif
 
-#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_stats, nngp_field_diag, nngp_field_diag_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
+#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_probs, nngp_summary_stats, nngp_field_diag, nngp_field_diag_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
 #define NNGP_SHARD_ID_BYTES 128 /* RCCL unique id */
 #define NNGP_IPC_HANDLE_BYTES 192 /* HIP IPC handles of a tile shard's granule buffer, w replica, flags */
 
@@ -421,7 +422,31 @@ int nngp_shard_sync(nngp_ctx* ctx);
 int nngp_summary(int device, const double* const* blocks, const long long* block_rows,
                  int n_blocks, long long n, const double* row_offset, int chunk_cols,
                  double* out);
-/* Measurement: the calling thread's last successful summary -- HIP-event times
+/* The same summary with the quantiles chosen by the caller and exceedance
+ * probabilities, the usual product of a pollution map (the reference's last
+ * step, Heavy_metals/Results_analysis.R, maps the field's summary): blocks,
+ * block_rows, n, row_offset, chunk_cols, device, staging and the row limit are
+ * nngp_summary's.  probs: n_probs (0..16) probabilities in [0, 1], in any
+ * order, repeats allowed; thresholds: n_thresholds (0..8) values, +-inf
+ * allowed; either array may be NULL when its count is 0.
+ * out: n x (2 + n_probs + n_thresholds) column-major: mean, the type-7
+ * quantiles in the order of probs (0 and 1 are the exact minimum and
+ * maximum), sd, then P(x > thresholds[k]) = count(x > t) / rows -- a strict
+ * compare of the values summarised (after row_offset), an integer count and
+ * one division.  probs = (0.025, 0.5, 0.975) without thresholds gives
+ * nngp_summary's matrix bit for bit.  A quantile's bits depend on its column
+ * and its own probability only, an exceedance column on its threshold only:
+ * not on what else was asked, nor on n, the chunking or the column's
+ * position.  A column holding a NaN gives NaNs in every output.
+ * NNGP_ERR_ARG (before any HIP call): what nngp_summary rejects; n_probs
+ * outside 0..16, n_thresholds outside 0..8, a null array with a positive
+ * count, a probability that is NaN or outside [0, 1], a NaN threshold. */
+int nngp_summary_probs(int device, const double* const* blocks, const long long* block_rows,
+                       int n_blocks, long long n, const double* row_offset, int chunk_cols,
+                       const double* probs, int n_probs, const double* thresholds, int n_thresholds,
+                       double* out);
+/* Measurement: the calling thread's last successful summary (nngp_summary or
+ * nngp_summary_probs, whichever ran last) -- HIP-event times
  * of its staging copies and of its kernels (each summed over the chunks; they
  * overlap, so the sum can exceed the call's wall time), the bytes staged and
  * the chunk width used.  Any pointer may be NULL.  NNGP_ERR_STATE: none yet.

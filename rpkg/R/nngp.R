@@ -98,10 +98,18 @@ nngp_device_normals <- function(device, seed, sweep, n)
   .Call(C_nngp_device_normals, as.integer(device), as.double(seed), as.double(sweep), as.integer(n))
 # get_summary (Scripts/mcmc_nngp_estimate.R:1-6) of a samples x locations matrix on the device:
 # n x 5 with columns mean, q0.025, median, q0.975, sd (type-7 quantiles, as quantile()'s default)
-nngp_get_summary <- function(samples, device = -1L) {
+# With probs (up to 16 probabilities in [0, 1], any order) or thresholds (up to 8 values) given:
+# n x (2 + Q + K) with columns mean, q<p>..., sd, p_gt_<t>... -- the type-7 quantiles in the order of probs
+# (NULL: 0.025, 0.5, 0.975) and the exceedance fractions mean(x > t) per location.  Both NULL: the call above.
+nngp_get_summary <- function(samples, device = -1L, probs = NULL, thresholds = NULL) {
   if (!is.matrix(samples)) samples <- matrix(samples, ncol = 1)
   storage.mode(samples) <- "double"
-  .Call(C_nngp_summary, as.integer(device), samples)
+  if (is.null(probs) && is.null(thresholds)) return(.Call(C_nngp_summary, as.integer(device), samples))
+  probs <- if (is.null(probs)) c(0.025, 0.5, 0.975) else as.double(probs)
+  thresholds <- as.double(thresholds)
+  out <- .Call(C_nngp_summary_probs, as.integer(device), samples, probs, thresholds)
+  colnames(out) <- c("mean", sprintf("q%g", probs), "sd", sprintf("p_gt_%g", thresholds))
+  out
 }
 # HIP-event times (ms), staged bytes and chunk width of the last nngp_get_summary
 nngp_summary_stats <- function() .Call(C_nngp_summary_stats)

@@ -465,6 +465,29 @@ SEXP C_nngp_summary(SEXP device, SEXP samples) {
   return out;
 }
 
+/* The same with chosen quantiles and exceedance probabilities
+ * (nngp_summary_probs): probs and thresholds are numeric vectors (length 0
+ * allowed); -> n x (2 + length(probs) + length(thresholds)): mean, the
+ * quantiles in the order of probs, sd, P(x > thresholds[k]).  The R wrapper
+ * names the columns. */
+SEXP C_nngp_summary_probs(SEXP device, SEXP samples, SEXP probs, SEXP thresholds) {
+  if (TYPEOF(samples) != REALSXP || !Rf_isMatrix(samples)) Rf_error("nngp: samples must be a numeric matrix");
+  if (TYPEOF(probs) != REALSXP || TYPEOF(thresholds) != REALSXP) Rf_error("nngp: probs and thresholds must be numeric");
+  const int S = Rf_nrows(samples), n = Rf_ncols(samples);
+  const int n_probs = (int)XLENGTH(probs), n_thr = (int)XLENGTH(thresholds);
+  if (n_probs > 16 || n_thr > 8) Rf_error("nngp: at most 16 probs and 8 thresholds");
+  SEXP rows = PROTECT(Rf_allocVector(REALSXP, (R_xlen_t)S * n));
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n, 2 + n_probs + n_thr));
+  nngp_rows_to_colmajor(REAL(samples), REAL(rows), n, n, S);
+  const double* block = REAL(rows);
+  const long long block_rows = S;
+  check(nngp_summary_probs(as_int(device), &block, &block_rows, 1, n, NULL, 0, n_probs ? REAL(probs) : NULL, n_probs,
+                           n_thr ? REAL(thresholds) : NULL, n_thr, REAL(out)),
+        NULL);
+  UNPROTECT(2);
+  return out;
+}
+
 /* the last summary's HIP-event times (ms), staged bytes and chunk width */
 SEXP C_nngp_summary_stats(void) {
   static const char* names[4] = {"copy_ms", "kernel_ms", "staged_bytes", "chunk_cols"};
@@ -954,6 +977,7 @@ static const R_CallMethodDef call_methods[] = {
     E(C_nngp_tri_rescues, 1),
     E(C_nngp_device_normals, 4),
     E(C_nngp_summary, 2),
+    E(C_nngp_summary_probs, 4),
     E(C_nngp_summary_stats, 0),
     E(C_nngp_field_diag, 2),
     E(C_nngp_field_diag_stats, 0),
