@@ -12,8 +12,9 @@ from .shard import ShardContext, init_shard_comm, sweep_chains_group  # noqa: F4
 from .initialize import mcmc_nngp_initialize  # noqa: F401
 from .update_gaussian import mcmc_nngp_update_Gaussian, ll_compressed_sparse_chol  # noqa: F401
 from .run import mcmc_nngp_run  # noqa: F401
-from .estimate import mcmc_nngp_estimate, get_summary, summary_columns  # noqa: F401
-from .predict import mcmc_nngp_predict_field, mcmc_nngp_predict_fixed_effects  # noqa: F401
+from .estimate import mcmc_nngp_estimate, get_summary, summary_columns, effects_summary, effects_stats  # noqa: F401
+from .predict import (mcmc_nngp_predict_field, mcmc_nngp_predict_fixed_effects,  # noqa: F401
+                      mcmc_nngp_predict_response)
 from .diagnose import Gelman_Rubin_Brooks, ESS, Field_diagnostics, field_diagnostics  # noqa: F401
 
 __all__ = [
@@ -21,5 +22,5 @@ __all__ = [
     "mcmc_nngp_estimate", "mcmc_nngp_predict_field", "mcmc_nngp_predict_fixed_effects",
     "ll_compressed_sparse_chol", "ChainContext", "find_ordered_nn", "naive_greedy_coloring",
     "order_maxmin", "Gelman_Rubin_Brooks", "ESS", "get_summary", "summary_columns",
-    "Field_diagnostics", "field_diagnostics",
+    "Field_diagnostics", "field_diagnostics", "effects_summary", "effects_stats", "mcmc_nngp_predict_response",
 ]

@@ -43,7 +43,8 @@ ABI_SYMBOLS = (
     "nngp_factor_chains", "nngp_loglik_chains", "nngp_field_response_ratio_chains",
     "nngp_sum_squared_residuals_chains", "nngp_loglik_pair_chains",
     "nngp_ancillary_step_chains", "nngp_sufficient_step_chains",
-    "nngp_summary", "nngp_summary_probs", "nngp_summary_stats", "nngp_field_diag", "nngp_field_diag_stats",
+    "nngp_summary", "nngp_summary_probs", "nngp_summary_stats", "nngp_effects_summary", "nngp_effects_stats",
+    "nngp_field_diag", "nngp_field_diag_stats",
     "nngp_predict_field", "nngp_predict_stats",
     "nngp_design_set", "nngp_design_mean_stats_chains", "nngp_design_interweave_stats_chains",
     "nngp_design_commit_chains", "nngp_get_mu",
@@ -151,6 +152,11 @@ def _load():
                                      C.c_int, _vp, C.c_int, _vp, C.c_int, _dp]
     L.nngp_summary_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong),
                                      C.POINTER(C.c_int)]
+    L.nngp_effects_summary.argtypes = [C.c_int, _vp, C.c_longlong, C.c_int, _vp, C.c_longlong, C.POINTER(_vp),
+                                       C.POINTER(C.c_longlong), C.c_int, _vp, C.c_uint64, _vp, C.c_int, _vp, C.c_int,
+                                       _vp, C.c_int, _vp, _vp]
+    L.nngp_effects_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_longlong), C.POINTER(C.c_int)]
     L.nngp_field_diag.argtypes = [C.c_int, C.POINTER(_vp), C.c_int, C.c_longlong, C.c_longlong, _vp, C.c_int, _dp, _vp]
     L.nngp_field_diag_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong),
                                         C.POINTER(C.c_int)]

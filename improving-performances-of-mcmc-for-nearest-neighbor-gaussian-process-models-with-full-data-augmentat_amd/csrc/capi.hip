@@ -22,6 +22,7 @@
 #include "kernels.h"
 #include "rec_stream.h"
 #include "summary.h"
+#include "effects.h"
 #include "field_diag_run.h"
 #include "predict.h"
 #include "regress.h"
@@ -307,6 +308,7 @@ constexpr int kTileTarget = 2048;  // locations per tile (default tile count: n 
 
 thread_local std::string g_err;
 thread_local SummaryStats g_summary_stats;  // of this thread's last successful nngp_summary / nngp_summary_probs
+thread_local EffectsStats g_effects_stats;  // of this thread's last successful nngp_effects_summary
 thread_local FieldDiagStats g_field_diag_stats;  // of this thread's last successful nngp_field_diag
 thread_local PredictStats g_predict_stats;  // of this thread's last successful nngp_predict_field
 
@@ -3279,6 +3281,31 @@ int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_byt
   if (kernel_ms) *kernel_ms = g_summary_stats.kernel_ms;
   if (staged_bytes) *staged_bytes = g_summary_stats.staged_bytes;
   if (chunk_cols) *chunk_cols = g_summary_stats.chunk_cols;
+  return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- effects summary
+int nngp_effects_summary(int device, const double* coef, long long n_samples, int q, const double* X, long long n,
+                         const double* const* addend_blocks, const long long* block_rows, int n_blocks,
+                         const double* noise_sd, uint64_t seed, const uint64_t* counter, int chunk_cols,
+                         const double* probs, int n_probs, const double* thresholds, int n_thresholds, double* out,
+                         double* samples_out) {
+  const EffectsArgs a{device, coef, n_samples, q, X, n, addend_blocks, block_rows, n_blocks, noise_sd, seed, counter,
+                      chunk_cols, probs, n_probs, thresholds, n_thresholds, out, samples_out};
+  std::string err;
+  const int st = effects_run(a, &g_effects_stats, err);
+  return st == NNGP_OK ? NNGP_OK : fail_msg(nullptr, st, err);
+}
+
+int nngp_effects_stats(double* copy_ms, double* generate_ms, double* kernel_ms, long long* staged_bytes,
+                       int* chunk_cols) {
+  if (g_effects_stats.n_chunks < 1)
+    return fail_msg(nullptr, NNGP_ERR_STATE, "effects_stats: no effects_summary on this thread yet");
+  if (copy_ms) *copy_ms = g_effects_stats.copy_ms;
+  if (generate_ms) *generate_ms = g_effects_stats.generate_ms;
+  if (kernel_ms) *kernel_ms = g_effects_stats.kernel_ms;
+  if (staged_bytes) *staged_bytes = g_effects_stats.staged_bytes;
+  if (chunk_cols) *chunk_cols = g_effects_stats.chunk_cols;
   return NNGP_OK;
 }
 

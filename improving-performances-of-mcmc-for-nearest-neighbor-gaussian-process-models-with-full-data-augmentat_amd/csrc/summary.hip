@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "../../include/nngp.h"
+#include "summary_launch.h"
 #include "summary_select.h"
 
 namespace nngp {
@@ -51,14 +52,6 @@ __global__ __launch_bounds__(kSummaryBlock) void summary_kernel(const double* __
 #pragma unroll
   for (int q = 0; q < kSummaryCols; ++q) out[q * n + c0 + c] = r[q];
 }
-
-// The request of nngp_summary_probs, a kernel argument: the same for every
-// lane, so the probabilities and thresholds are scalar loads.
-struct SummaryRequest {
-  double probs[kSummaryProbsMax];
-  double thr[kSummaryThrMax];
-  int n_probs, n_thr;
-};
 
 // out: n x (2 + n_probs + n_thr) column-major; columns c0 .. c0 + w - 1.
 // With row offsets the kernel is held to 4 waves per SIMD (110 VGPRs instead
@@ -160,27 +153,9 @@ int summary_stage(int device, const double* const* blocks, const long long* bloc
   };
   if (e != hipSuccess) return hip_fail("hipSetDevice");
 
-  // chunk width W (columns per launch).  Automatic: the two staging buffers
-  // stay within kSummaryStageBudget (but never below one wavefront of
-  // columns); a matrix that would fit one chunk is still cut into about four,
-  // so that copies and kernels overlap, unless that leaves fewer than 64 Ki
-  // columns (4 waves on each of 256 CUs) per launch.
-  long long W = chunk_cols;
-  if (W == 0) {
-    W = (long long)(kSummaryStageBudget / 2 / sizeof(double)) / S / kSummaryBlock * kSummaryBlock;
-    const long long quarter = (n / 4 + kSummaryBlock - 1) / kSummaryBlock * kSummaryBlock;
-    W = std::min(W, std::max(65536LL, quarter));
-    W = std::max(W, 64LL);
-  }
-  W = std::min(W, n);
-  const int bits = [] {
-    const char* s = std::getenv("NNGP_SUMMARY_BITS");
-    return s ? std::atoi(s) : 4;  // 4-bit digits: 16 passes; measured ahead of 2 bits x 32
-  }();
-  if (bits != 2 && bits != 4) {
-    err = "NNGP_SUMMARY_BITS must be 2 or 4";
-    return NNGP_ERR_ARG;
-  }
+  const long long W = summary_chunk_width(S, n, chunk_cols);
+  int bits = 0;
+  if (const int rc = summary_digit_bits(&bits, err)) return rc;
 
   SummaryDev D;
   const size_t chunk_bytes = sizeof(double) * (size_t)S * (size_t)W;
@@ -244,10 +219,7 @@ int summary_stage(int device, const double* const* blocks, const long long* bloc
     st.staged_bytes += (long long)sizeof(double) * S * w;
     SUMMARY_HIP(hipStreamWaitEvent(D.run_st, D.copy1[b], 0));
     SUMMARY_HIP(hipEventRecord(D.run0[b], D.run_st));
-    if (bits == 4)
-      SUMMARY_HIP(launch_summary<4>(D.run_st, D.buf[b], D.off, S, w, W, req, D.out, n, c0));
-    else
-      SUMMARY_HIP(launch_summary<2>(D.run_st, D.buf[b], D.off, S, w, W, req, D.out, n, c0));
+    SUMMARY_HIP(summary_launch(bits, D.run_st, D.buf[b], D.off, S, w, W, req, D.out, n, c0));
     SUMMARY_HIP(hipEventRecord(D.run1[b], D.run_st));
   }
   st.n_chunks = (int)k;
@@ -261,6 +233,63 @@ int summary_stage(int device, const double* const* blocks, const long long* bloc
 
 }  // namespace
 
+long long summary_chunk_width(long long S, long long n, int chunk_cols) {
+  long long W = chunk_cols;
+  if (W == 0) {
+    W = (long long)(kSummaryStageBudget / 2 / sizeof(double)) / S / kSummaryBlock * kSummaryBlock;
+    const long long quarter = (n / 4 + kSummaryBlock - 1) / kSummaryBlock * kSummaryBlock;
+    W = std::min(W, std::max(65536LL, quarter));
+    W = std::max(W, 64LL);
+  }
+  return std::min(W, n);
+}
+
+int summary_digit_bits(int* bits, std::string& err) {
+  const char* s = std::getenv("NNGP_SUMMARY_BITS");
+  *bits = s ? std::atoi(s) : 4;  // 4-bit digits: 16 passes; measured ahead of 2 bits x 32
+  if (*bits != 2 && *bits != 4) {
+    err = "NNGP_SUMMARY_BITS must be 2 or 4";
+    return NNGP_ERR_ARG;
+  }
+  return NNGP_OK;
+}
+
+hipError_t summary_launch(int bits, hipStream_t st, const double* x, const double* off, long long S, int w,
+                          long long pitch, const SummaryRequest* req, double* out, long long n, long long c0) {
+  return bits == 4 ? launch_summary<4>(st, x, off, S, w, pitch, req, out, n, c0)
+                   : launch_summary<2>(st, x, off, S, w, pitch, req, out, n, c0);
+}
+
+int summary_make_request(const double* probs, int n_probs, const double* thresholds, int n_thresholds,
+                         SummaryRequest* req, std::string& err) {
+  if (n_probs < 0 || n_probs > kSummaryProbsMax || n_thresholds < 0 || n_thresholds > kSummaryThrMax) {
+    err = "summary: n_probs must be 0..16 and n_thresholds 0..8";
+    return NNGP_ERR_ARG;
+  }
+  if ((n_probs > 0 && !probs) || (n_thresholds > 0 && !thresholds)) {
+    err = "summary: null probs or thresholds with a positive count";
+    return NNGP_ERR_ARG;
+  }
+  *req = {};
+  req->n_probs = n_probs;
+  req->n_thr = n_thresholds;
+  for (int i = 0; i < n_probs; ++i) {
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) {  // a NaN fails both compares
+      err = "summary: a probability is NaN or outside [0, 1]";
+      return NNGP_ERR_ARG;
+    }
+    req->probs[i] = probs[i];
+  }
+  for (int k = 0; k < n_thresholds; ++k) {
+    if (thresholds[k] != thresholds[k]) {
+      err = "summary: a threshold is NaN";
+      return NNGP_ERR_ARG;
+    }
+    req->thr[k] = thresholds[k];
+  }
+  return NNGP_OK;
+}
+
 int summary_run(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
                 const double* row_offset, int chunk_cols, double* out, SummaryStats* stats, std::string& err) {
   return summary_stage(device, blocks, block_rows, n_blocks, n, row_offset, chunk_cols, nullptr, kSummaryCols, out, stats,
@@ -270,31 +299,8 @@ int summary_run(int device, const double* const* blocks, const long long* block_
 int summary_run_probs(int device, const double* const* blocks, const long long* block_rows, int n_blocks, long long n,
                       const double* row_offset, int chunk_cols, const double* probs, int n_probs,
                       const double* thresholds, int n_thresholds, double* out, SummaryStats* stats, std::string& err) {
-  if (n_probs < 0 || n_probs > kSummaryProbsMax || n_thresholds < 0 || n_thresholds > kSummaryThrMax) {
-    err = "summary: n_probs must be 0..16 and n_thresholds 0..8";
-    return NNGP_ERR_ARG;
-  }
-  if ((n_probs > 0 && !probs) || (n_thresholds > 0 && !thresholds)) {
-    err = "summary: null probs or thresholds with a positive count";
-    return NNGP_ERR_ARG;
-  }
-  SummaryRequest req = {};
-  req.n_probs = n_probs;
-  req.n_thr = n_thresholds;
-  for (int i = 0; i < n_probs; ++i) {
-    if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) {  // a NaN fails both compares
-      err = "summary: a probability is NaN or outside [0, 1]";
-      return NNGP_ERR_ARG;
-    }
-    req.probs[i] = probs[i];
-  }
-  for (int k = 0; k < n_thresholds; ++k) {
-    if (thresholds[k] != thresholds[k]) {
-      err = "summary: a threshold is NaN";
-      return NNGP_ERR_ARG;
-    }
-    req.thr[k] = thresholds[k];
-  }
+  SummaryRequest req;
+  if (const int rc = summary_make_request(probs, n_probs, thresholds, n_thresholds, &req, err)) return rc;
   return summary_stage(device, blocks, block_rows, n_blocks, n, row_offset, chunk_cols, &req, 2 + n_probs + n_thresholds,
                        out, stats, err);
 }

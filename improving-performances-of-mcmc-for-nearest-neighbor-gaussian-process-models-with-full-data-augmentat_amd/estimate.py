@@ -137,6 +137,113 @@ def summary_stats():
     return {"copy_ms": cp.value, "kernel_ms": kn.value, "staged_bytes": by.value, "chunk_cols": w.value}
 
 
+def _row_blocks(blocks, what):
+    """A 2-D array or a list of 2-D arrays as float64 row-contiguous blocks
+    (a block that is one already is passed where it lies)."""
+    if not (isinstance(blocks, (list, tuple)) and len(blocks) and np.ndim(blocks[0]) == 2):
+        blocks = [np.asarray(blocks)]
+    out = []
+    for b in blocks:
+        b = np.asarray(b)
+        if b.ndim != 2:
+            raise ValueError(f"{what}: every block must be 2-D")
+        if b.dtype != np.float64 or not b.flags.c_contiguous:
+            b = np.ascontiguousarray(b, np.float64)
+        out.append(b)
+    return out
+
+
+def effects_summary(coef, X, addend=None, noise_sd=None, seed=0, counter=None, probs=None, thresholds=None,
+                    backend="host", device=-1, chunk_cols=0, return_samples=False):
+    """The summary of the samples ``coef @ X.T (+ addend) (+ noise)`` per
+    location (predict.R:92-102: beta_matrix[, subset] %*% t(X_pred) and its
+    get_summary), without the samples on the host when ``backend="hip"``.
+
+    ``coef``: S x q coefficient samples; ``X``: n x q design rows of the new
+    locations (an array whose transpose is C-contiguous float64 is passed where
+    it lies); ``addend``: an S x n array or a list of blocks stacking to S rows
+    (the predicted field's per-chain samples); ``noise_sd`` (S): sample s gets
+    noise_sd[s] * z with z the Philox / AS241 normals of
+    (``seed``, ``counter[s]``) -- nngp_device_normals -- ``counter`` defaulting
+    to 0 .. S-1.  ``probs`` / ``thresholds`` are get_summary's.
+
+    ``backend="host"`` is numpy (the product, the sums, the host get_summary);
+    its normals still come from the library, so noise needs a device.
+    ``backend="hip"`` is nngp_effects_summary: the samples are generated chunk
+    by chunk on ``device`` by the arithmetic include/nngp.h states and
+    summarised there; ``chunk_cols`` as for get_summary.  Returns the (n,
+    columns) summary, or (summary, samples) with ``return_samples=True``
+    (hip: the device's own values)."""
+    if backend not in ("host", "hip"):
+        raise ValueError(f"effects_summary: backend must be 'host' or 'hip', not {backend!r}")
+    req = _summary_request(probs, thresholds)
+    coef = np.asarray(coef, np.float64)
+    X = np.asarray(X, np.float64)
+    if coef.ndim != 2 or X.ndim != 2 or coef.shape[1] != X.shape[1]:
+        raise ValueError("effects_summary: coef must be S x q and X n x q")
+    S, n = coef.shape[0], X.shape[0]
+    blocks = None if addend is None else _row_blocks(addend, "effects_summary")
+    if blocks is not None and (any(b.shape[1] != n for b in blocks) or sum(b.shape[0] for b in blocks) != S):
+        raise ValueError("effects_summary: the addend must stack to S x n")
+    sd = cnt = None
+    if noise_sd is not None:
+        sd = np.ascontiguousarray(np.asarray(noise_sd, np.float64).reshape(-1))
+        cnt = np.arange(S, dtype=np.uint64) if counter is None else np.ascontiguousarray(counter, np.uint64).reshape(-1)
+        if sd.size != S or cnt.size != S:
+            raise ValueError("effects_summary: noise_sd and counter need one entry per sample")
+    seed = int(seed) & (2 ** 64 - 1)
+    if backend == "hip":
+        return _effects_hip(coef, X, blocks, sd, seed, cnt, req, device, chunk_cols, return_samples)
+    samples = coef @ X.T
+    if blocks is not None:
+        samples = samples + np.vstack(blocks)
+    if sd is not None:
+        from . import _lib
+
+        z = np.empty((S, n))
+        for s in range(S):
+            _lib.check(_lib.lib.nngp_device_normals(int(device), seed, int(cnt[s]), n, z[s]))
+        samples = samples + sd[:, None] * z
+    widen = {} if probs is None and thresholds is None else {"probs": probs, "thresholds": thresholds}
+    summary = get_summary(samples, **widen)
+    return (summary, samples) if return_samples else summary
+
+
+def _effects_hip(coef, X, blocks, sd, seed, cnt, req, device, chunk_cols, return_samples):
+    import ctypes as C
+
+    from . import _lib
+
+    p, t = req
+    (S, q), n = coef.shape, X.shape[0]
+    coef_cm, X_cm = _lib.colmajor(coef, np.float64), _lib.colmajor(X, np.float64)
+    nb = 0 if blocks is None else len(blocks)
+    rows = (C.c_longlong * max(nb, 1))(*[b.shape[0] for b in blocks or ()])
+    ptrs = (C.c_void_p * max(nb, 1))(*[b.ctypes.data for b in blocks or ()])
+    out = np.empty((2 + p.size + t.size, max(n, 1)))  # n x (2 + Q + K) column-major
+    samples = np.empty((S, n)) if return_samples else None
+    _lib.check(_lib.lib.nngp_effects_summary(
+        int(device), coef_cm.ctypes.data, S, q, X_cm.ctypes.data, n, ptrs if nb else None, rows if nb else None, nb,
+        None if sd is None else sd.ctypes.data, seed, None if cnt is None else cnt.ctypes.data, int(chunk_cols),
+        p.ctypes.data if p.size else None, p.size, t.ctypes.data if t.size else None, t.size,
+        out.ctypes.data, None if samples is None else samples.ctypes.data))
+    summary = np.ascontiguousarray(out.T)
+    return (summary, samples) if return_samples else summary
+
+
+def effects_stats():
+    """HIP-event times and staging size of this thread's last device
+    effects_summary (nngp_effects_stats)."""
+    import ctypes as C
+
+    from . import _lib
+
+    cp, gn, kn, by, w = C.c_double(), C.c_double(), C.c_double(), C.c_longlong(), C.c_int()
+    _lib.check(_lib.lib.nngp_effects_stats(C.byref(cp), C.byref(gn), C.byref(kn), C.byref(by), C.byref(w)))
+    return {"copy_ms": cp.value, "generate_ms": gn.value, "kernel_ms": kn.value, "staged_bytes": by.value,
+            "chunk_cols": w.value}
+
+
 def _plogis(x):
     return 1 / (1 + np.exp(-x))
 

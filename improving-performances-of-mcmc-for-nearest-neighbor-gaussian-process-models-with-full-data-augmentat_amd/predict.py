@@ -1,5 +1,6 @@
 """mcmc_nngp_predict_field / mcmc_nngp_predict_fixed_effects -- host mirror of
-Scripts/mcmc_nngp_predict.R:1-104 ("next").
+Scripts/mcmc_nngp_predict.R:1-104 ("next"), and
+mcmc_nngp_predict_response, the sum of the two per stored iteration.
 
 Per saved sample the field is predicted with the device factor build on the
 stacked locations and the device sparse triangular solve
@@ -19,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .context import ChainContext
-from .estimate import get_summary, summary_columns
+from .estimate import effects_summary, get_summary, summary_columns
 from .graph import find_ordered_nn, naive_greedy_coloring
 from .model import covparms
 
@@ -208,11 +209,11 @@ def _predict_field_batched(L, predicted_locs, burn_in, m, seed, device, z_new, s
             **_field_summary(out, summary_backend, device, summary_probs, summary_thresholds)}
 
 
-def mcmc_nngp_predict_fixed_effects(mcmc_nngp_list, X_predicted, burn_in=0.5, n_cores=1,
-                                    match_field_thinning=True, add_intercept=False):
+def _stored_coef(L, X_predicted, burn_in, match_field_thinning, add_intercept):
+    """predict.R:67-91: the design rows of the new locations (n_pred x q) and,
+    per chain, the de-centred cbind(beta_0, beta)[stored, subset] rows."""
     from .initialize import _model_matrix
 
-    L = mcmc_nngp_list
     first = next(iter(L["records"].values()))
     stored = first["saved_field"] if match_field_thinning else np.arange(1, int(first["iterations"][-1, 0]) + 1)
     stored = stored[stored > burn_in * stored.max()].astype(int)
@@ -223,12 +224,91 @@ def mcmc_nngp_predict_fixed_effects(mcmc_nngp_list, X_predicted, burn_in=0.5, n_
         mm, names = mm[:, 1:], names[1:]
     allnames = ["beta_0"] + list(L["X"].get("names", []))
     subset = [allnames.index(nm) for nm in names]
-    out = []
-    for kc, chain in enumerate(L["records"].values()):
+    coef = []
+    for chain in L["records"].values():
         bm = np.column_stack([chain["params"]["beta_0"]] + ([chain["params"]["beta"]] if "beta" in chain["params"] else []))
         bm = bm[stored - 1].copy()
         if bm.shape[1] > 1:
             bm[:, 0] = bm[:, 0] - bm[:, 1:] @ L["X"]["X_mean"]
-        out.append(bm[:, subset] @ mm.T)
-    return {"X_predicted": X_predicted, "predicted_fixed_effects_samples": out,
-            "predicted_fixed_effects_summary": get_summary(np.vstack(out))}
+        coef.append(bm[:, subset])
+    return mm, coef, stored
+
+
+def mcmc_nngp_predict_fixed_effects(mcmc_nngp_list, X_predicted, burn_in=0.5, n_cores=1,
+                                    match_field_thinning=True, add_intercept=False, summary_backend="host",
+                                    device=-1, summary_probs=None, summary_thresholds=None, keep_samples=True):
+    """predict.R:62-104.  ``summary_backend="hip"``: the samples are generated
+    and summarised on ``device`` by one effects_summary call over the chains'
+    stacked coefficient rows (nngp_effects_summary); with ``keep_samples=False``
+    predicted_fixed_effects_samples is None and no n_samples x n_pred array
+    exists on the host, with ``keep_samples=True`` the per-chain arrays are the
+    device's own values.  ``summary_probs`` / ``summary_thresholds`` are
+    get_summary's ``probs`` / ``thresholds`` (both backends); with either
+    given, predicted_fixed_effects_summary_columns names the columns."""
+    if summary_backend not in ("host", "hip"):
+        raise ValueError(f"mcmc_nngp_predict_fixed_effects: summary_backend must be 'host' or 'hip', "
+                         f"not {summary_backend!r}")
+    mm, coef, _ = _stored_coef(mcmc_nngp_list, X_predicted, burn_in, match_field_thinning, add_intercept)
+    widen = {} if summary_probs is None and summary_thresholds is None \
+        else {"probs": summary_probs, "thresholds": summary_thresholds}
+    if summary_backend == "hip":
+        got = effects_summary(np.vstack(coef), mm, backend="hip", device=device, return_samples=keep_samples, **widen)
+        summary, out = got if keep_samples else (got, None)
+        if keep_samples:
+            out = np.split(out, np.cumsum([len(c) for c in coef])[:-1])
+    else:
+        out = [c @ mm.T for c in coef]
+        summary = get_summary(np.vstack(out), **widen)
+        if not keep_samples:
+            out = None
+    res = {"X_predicted": X_predicted, "predicted_fixed_effects_samples": out,
+           "predicted_fixed_effects_summary": summary}
+    if widen:
+        res["predicted_fixed_effects_summary_columns"] = summary_columns(summary_probs, summary_thresholds)
+    return res
+
+
+PHILOX_RESPONSE_MIX = 0xD1B54A32D192ED03
+
+
+def mcmc_nngp_predict_response(mcmc_nngp_list, predicted_locs, X_predicted, burn_in=0.5, m=10, seed=1, noise=False,
+                               summary_backend="hip", device=-1, summary_probs=None, summary_thresholds=None,
+                               **predict_field_kw):
+    """The map the reference's pieces add up to: intercept + fixed effects +
+    predicted field (+ observation noise) at new locations, summarised per
+    location with quantiles and P(value > t).
+
+    The field samples come from mcmc_nngp_predict_field(engine="batched")
+    (``m``, ``seed``, ``device`` and ``predict_field_kw`` go there); they are
+    field - beta_0.  One effects_summary call then adds, per stored iteration
+    (the field's thinning), the de-centred cbind(beta_0, beta) row times
+    cbind(1, X_predicted) -- the beta_0 column alone when the model has no
+    covariates (``X_predicted=None``) -- to that iteration's field sample, the
+    per-chain field arrays being its addend blocks, read where they lie.
+    ``noise=True`` adds exp(log_noise_variance / 2) times a Philox / AS241
+    normal: key (seed + 0xD1B54A32D192ED03) mod 2^64, counter = the sample's
+    ordinal in the chains' stack.  ``summary_backend="host"`` does the same
+    through numpy.  Returns predicted_locs, predicted_response_summary, its
+    column names and the field prediction's own dict."""
+    if summary_backend not in ("host", "hip"):
+        raise ValueError(f"mcmc_nngp_predict_response: summary_backend must be 'host' or 'hip', "
+                         f"not {summary_backend!r}")
+    L = mcmc_nngp_list
+    predict_field_kw.setdefault("summary_backend", summary_backend)
+    field = mcmc_nngp_predict_field(L, predicted_locs, burn_in=burn_in, m=m, seed=seed, device=device,
+                                    engine="batched", **predict_field_kw)
+    n_pred = field["predicted_locs"].shape[0]
+    if X_predicted is None:
+        X_predicted = np.zeros((n_pred, 0))
+    mm, coef, stored = _stored_coef(L, X_predicted, burn_in, True, True)
+    kw = {}
+    if noise:
+        kw = {"noise_sd": np.concatenate([np.exp(0.5 * c["params"]["log_noise_variance"][stored - 1, 0])
+                                          for c in L["records"].values()]),
+              "seed": (int(seed) + PHILOX_RESPONSE_MIX) % 2 ** 64,
+              "counter": np.arange(sum(len(c) for c in coef), dtype=np.uint64)}
+    summary = effects_summary(np.vstack(coef), mm, addend=field["predicted_field_samples"], probs=summary_probs,
+                              thresholds=summary_thresholds, backend=summary_backend, device=device, **kw)
+    return {"predicted_locs": field["predicted_locs"], "predicted_response_summary": summary,
+            "predicted_response_summary_columns": summary_columns(summary_probs, summary_thresholds),
+            "field_prediction": field}

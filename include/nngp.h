@@ -41,6 +41,8 @@
  *   nngp_summary ............. get_summary, Scripts/mcmc_nngp_estimate.R:1-6 (res$field,
  *                              estimate.R:88-94; predicted_field_summary, predict.R:57-58)
  *   nngp_summary_probs ....... the same with chosen quantiles and exceedance probabilities
+ *   nngp_effects_summary ..... beta_matrix[, subset] %*% t(X_pred) and its get_summary,
+ *                              Scripts/mcmc_nngp_predict.R:92-102, the samples generated on the device
  *   nngp_field_diag .......... Individual_PSRF of Gelman_Rubin_Brooks and ESS,
  *                              Scripts/mcmc_nngp_diagnose.R:1-24,107-118, per field location
  *   nngp_predict_field ....... the per-sample body of mcmc_nngp_predict_field,
@@ -65,7 +67,7 @@
 extern "C" {
 #endif
 
-#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_probs, nngp_summary_stats, nngp_field_diag, nngp_field_diag_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
+#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_probs, nngp_summary_stats, nngp_effects_summary, nngp_effects_stats, nngp_field_diag, nngp_field_diag_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
 #define NNGP_SHARD_ID_BYTES 128 /* RCCL unique id */
 #define NNGP_IPC_HANDLE_BYTES 192 /* HIP IPC handles of a tile shard's granule buffer, w replica, flags */
 
@@ -455,6 +457,61 @@ int nngp_summary_probs(int device, const double* const* blocks, const long long*
  * call (its streams and events are gone when it returns), and
  * scripts/summary_time.py, the R wrapper and a C client all read them here. */
 int nngp_summary_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols);
+
+/* ---------- fixed-effect / response samples generated and summarised on the device (no context) ---------- */
+/* mcmc_nngp_predict_fixed_effects (Scripts/mcmc_nngp_predict.R:92-102) without the
+ * n_samples x n matrix beta_matrix[, subset] %*% t(X_pred) on the host: the samples
+ * are generated chunk by chunk in the device buffer that the kernels of
+ * nngp_summary_probs read, and summarised there.
+ * coef: n_samples x q column-major (R's beta_matrix[, beta_subset]); X: n x q
+ * column-major (the design rows of the n new locations).  Optional addend: the
+ * row-wise stack of n_blocks host blocks (nngp_summary's convention: block k is
+ * block_rows[k] x n row-major, pitch n, read where it lies); n_blocks == 0 with
+ * NULL arrays: none.  Optional noise: noise_sd (n_samples) and counter
+ * (n_samples); noise_sd == NULL: none.
+ * The value of sample s at location c is defined by its arithmetic, in this order:
+ *   acc = coef[s,0] * X[c,0]
+ *   acc = fma(coef[s,k], X[c,k], acc)      k = 1 .. q-1, in column order
+ *   acc = addend[s,c] + acc                with an addend
+ *   acc = fma(noise_sd[s], z, acc)         with noise; z = the Philox / AS241 normal
+ *                                          of (seed, counter[s], c), the value
+ *                                          nngp_device_normals returns at [c] for
+ *                                          sweep = counter[s]
+ * so it depends on (s, c) and its inputs alone: not on n, the chunking, the
+ * column's position or the other samples.  NaN and inf in coef, X or the addend
+ * propagate by IEEE rules (a NaN among a location's samples gives NaNs in that
+ * location's outputs, as nngp_summary_probs documents).
+ * out: n x (2 + n_probs + n_thresholds) column-major, the columns of
+ * nngp_summary_probs of these samples (bit for bit what it returns for them);
+ * probs and thresholds as there.  samples_out: n_samples x n row-major, or NULL;
+ * when given, every chunk's values are copied there, otherwise no sample leaves
+ * the device.
+ * Staging: coef and X are copied to the device once; per chunk of chunk_cols
+ * columns (0 = automatic, nngp_summary's rule: both chunk buffers within 1 GiB,
+ * never below 64 columns) only the addend's columns are copied, the copy of one
+ * chunk running beside the kernels of the chunk before; without an addend
+ * nothing is copied per chunk.  Device footprint: the two chunk buffers, X,
+ * coef and out.  device: HIP ordinal (-1: current); the calling thread's
+ * current device is the same after the call as before it.
+ * NNGP_ERR_ARG (before any HIP call): what nngp_summary_probs rejects for probs
+ * and thresholds; a null coef, X or out; n < 1; n_samples outside 1..2^31-1;
+ * q outside 1..1024; chunk_cols < 0; a null addend block, or addend rows that
+ * do not sum to n_samples; a NaN or negative noise_sd; noise_sd without
+ * counter; noise with n > 2^31-1 (z is indexed by an int). */
+int nngp_effects_summary(int device, const double* coef, long long n_samples, int q,
+                         const double* X, long long n,
+                         const double* const* addend_blocks, const long long* block_rows, int n_blocks,
+                         const double* noise_sd, uint64_t seed, const uint64_t* counter,
+                         int chunk_cols, const double* probs, int n_probs,
+                         const double* thresholds, int n_thresholds,
+                         double* out, double* samples_out);
+/* Measurement, as nngp_summary_stats: the calling thread's last successful
+ * nngp_effects_summary -- HIP-event times of the addend copies, the generator
+ * kernels and the summary kernels (each summed over the chunks), the addend
+ * bytes staged (0 without an addend) and the chunk width used.  Any pointer may
+ * be NULL.  NNGP_ERR_STATE: none yet. */
+int nngp_effects_stats(double* copy_ms, double* generate_ms, double* kernel_ms,
+                       long long* staged_bytes, int* chunk_cols);
 
 /* ---------- convergence diagnostics per field location (no context) ---------- */
 /* Individual_PSRF of Gelman_Rubin_Brooks and ESS (Scripts/mcmc_nngp_diagnose.R:1-24,

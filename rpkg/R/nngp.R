@@ -113,6 +113,27 @@ nngp_get_summary <- function(samples, device = -1L, probs = NULL, thresholds = N
 }
 # HIP-event times (ms), staged bytes and chunk width of the last nngp_get_summary
 nngp_summary_stats <- function() .Call(C_nngp_summary_stats)
+# The summary of coef %*% t(X) (+ addend) (+ noise_sd * normals) per location, the samples generated and summarised
+# on the device (Scripts/mcmc_nngp_predict.R:92-102 without the n_samples x n matrix in R's memory): coef S x q
+# (beta_matrix[, beta_subset]), X n x q (the design rows of the new locations), addend NULL or S x n (the predicted
+# field's samples), noise_sd NULL or S values with seed and counter (default 0 .. S-1: the Philox / AS241 normals of
+# nngp_device_normals(device, seed, counter[s], n)).  -> n x (2 + Q + K) with nngp_get_summary's columns
+# (probs NULL: 0.025, 0.5, 0.975)
+nngp_effects_summary <- function(coef, X, addend = NULL, noise_sd = NULL, seed = 0, counter = NULL, probs = NULL,
+                                 thresholds = NULL, device = -1L) {
+  coef <- as.matrix(coef) + 0
+  X <- as.matrix(X) + 0
+  probs <- if (is.null(probs)) c(0.025, 0.5, 0.975) else as.double(probs)
+  thresholds <- as.double(thresholds)
+  if (!is.null(noise_sd) && is.null(counter)) counter <- seq_len(nrow(coef)) - 1
+  out <- .Call(C_nngp_effects_summary, as.integer(device), coef, X, if (is.null(addend)) NULL else t(addend) + 0,
+               if (is.null(noise_sd)) NULL else as.double(noise_sd), as.double(seed),
+               if (is.null(counter)) NULL else as.double(counter), probs, thresholds)
+  colnames(out) <- c("mean", sprintf("q%g", probs), "sd", sprintf("p_gt_%g", thresholds))
+  out
+}
+# HIP-event times (ms), staged bytes and chunk width of the last nngp_effects_summary
+nngp_effects_stats <- function() .Call(C_nngp_effects_stats)
 # R-hat (Individual_PSRF of Gelman_Rubin_Brooks, n := saved rows) and effective sample size (ESS) of every
 # field location (Scripts/mcmc_nngp_diagnose.R:1-24,107-118) on the device.  chains: a list with one
 # samples x locations matrix per chain (the saved field rows after burn-in, centred); -> n x 5 with

@@ -507,6 +507,66 @@ SEXP C_nngp_summary_stats(void) {
   return out;
 }
 
+/* The summary of coef %*% t(X) (+ addend) (+ noise) per location with the
+ * samples generated on the device (nngp_effects_summary; predict.R:92-102):
+ * coef S x q and X n x q as R holds them; addend_t NULL or n x S, the TRANSPOSE
+ * of the S x n addend, so that R's column-major storage is the S row-major
+ * rows of n the library reads where they lie; noise_sd NULL or S values with
+ * seed and counter (S doubles); probs and thresholds numeric vectors (length 0
+ * allowed).  -> n x (2 + length(probs) + length(thresholds)); the R wrapper
+ * names the columns. */
+SEXP C_nngp_effects_summary(SEXP device, SEXP coef, SEXP X, SEXP addend_t, SEXP noise_sd, SEXP seed, SEXP counter,
+                            SEXP probs, SEXP thresholds) {
+  if (TYPEOF(coef) != REALSXP || !Rf_isMatrix(coef) || TYPEOF(X) != REALSXP || !Rf_isMatrix(X))
+    Rf_error("nngp: effects_summary: coef and X must be numeric matrices");
+  if (TYPEOF(probs) != REALSXP || TYPEOF(thresholds) != REALSXP) Rf_error("nngp: probs and thresholds must be numeric");
+  const int S = Rf_nrows(coef), q = Rf_ncols(coef), n = Rf_nrows(X);
+  const int n_probs = (int)XLENGTH(probs), n_thr = (int)XLENGTH(thresholds);
+  if (Rf_ncols(X) != q) Rf_error("nngp: effects_summary: coef and X differ in columns");
+  if (n_probs > 16 || n_thr > 8) Rf_error("nngp: at most 16 probs and 8 thresholds");
+  const int has_add = TYPEOF(addend_t) != NILSXP, has_noise = TYPEOF(noise_sd) != NILSXP;
+  if (has_add && (TYPEOF(addend_t) != REALSXP || !Rf_isMatrix(addend_t) || Rf_nrows(addend_t) != n ||
+                  Rf_ncols(addend_t) != S))
+    Rf_error("nngp: effects_summary: the addend must be S x n");
+  if (has_noise && (TYPEOF(noise_sd) != REALSXP || XLENGTH(noise_sd) != S))
+    Rf_error("nngp: effects_summary: noise_sd needs one value per sample");
+  /* 8-byte scratch in an R vector (released with the call, also on an R error) */
+  SEXP ctr_s = PROTECT(Rf_allocVector(REALSXP, has_noise ? S : 1));
+  uint64_t* ctr = NULL;
+  if (has_noise) {
+    ctr = (uint64_t*)(void*)REAL(ctr_s);
+    to_u64(counter, ctr, S);
+  }
+  const double* block = has_add ? REAL(addend_t) : NULL;
+  const long long block_rows = S;
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, n, 2 + n_probs + n_thr));
+  check(nngp_effects_summary(as_int(device), REAL(coef), S, q, REAL(X), n, has_add ? &block : NULL,
+                             has_add ? &block_rows : NULL, has_add ? 1 : 0, has_noise ? REAL(noise_sd) : NULL,
+                             has_noise ? (uint64_t)as_real(seed) : 0, ctr, 0, n_probs ? REAL(probs) : NULL, n_probs,
+                             n_thr ? REAL(thresholds) : NULL, n_thr, REAL(out), NULL),
+        NULL);
+  UNPROTECT(2);
+  return out;
+}
+
+/* the last effects summary's HIP-event times (ms), staged bytes and chunk width */
+SEXP C_nngp_effects_stats(void) {
+  static const char* names[5] = {"copy_ms", "generate_ms", "kernel_ms", "staged_bytes", "chunk_cols"};
+  double v[3] = {0, 0, 0};
+  long long bytes = 0;
+  int cols = 0;
+  check(nngp_effects_stats(&v[0], &v[1], &v[2], &bytes, &cols), NULL);
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, 5));
+  SEXP nm = PROTECT(Rf_allocVector(STRSXP, 5));
+  for (int i = 0; i < 3; ++i) REAL(out)[i] = v[i];
+  REAL(out)[3] = (double)bytes;
+  REAL(out)[4] = (double)cols;
+  for (int i = 0; i < 5; ++i) SET_STRING_ELT(nm, i, Rf_mkChar(names[i]));
+  Rf_setAttrib(out, R_NamesSymbol, nm);
+  UNPROTECT(2);
+  return out;
+}
+
 /* Per-location R-hat and effective sample size of the field samples
  * (Scripts/mcmc_nngp_diagnose.R:1-24,107-118).  chains_t: a list with one
  * n x S numeric matrix per chain, the TRANSPOSE of its S saved rows x n
@@ -979,6 +1039,8 @@ static const R_CallMethodDef call_methods[] = {
     E(C_nngp_summary, 2),
     E(C_nngp_summary_probs, 4),
     E(C_nngp_summary_stats, 0),
+    E(C_nngp_effects_summary, 9),
+    E(C_nngp_effects_stats, 0),
     E(C_nngp_field_diag, 2),
     E(C_nngp_field_diag_stats, 0),
     E(C_nngp_predict_field, 14),
