@@ -13,8 +13,10 @@ from .initialize import mcmc_nngp_initialize  # noqa: F401
 from .update_gaussian import mcmc_nngp_update_Gaussian, ll_compressed_sparse_chol  # noqa: F401
 from .run import mcmc_nngp_run  # noqa: F401
 from .estimate import mcmc_nngp_estimate, get_summary, summary_columns, effects_summary, effects_stats  # noqa: F401
+from .estimate import (POINTWISE_COLUMNS, pointwise_loglik, pointwise_loglik_stats,  # noqa: F401
+                       mcmc_nngp_criteria)
 from .predict import (mcmc_nngp_predict_field, mcmc_nngp_predict_fixed_effects,  # noqa: F401
-                      mcmc_nngp_predict_response)
+                      mcmc_nngp_predict_response, mcmc_nngp_score_response)
 from .diagnose import Gelman_Rubin_Brooks, ESS, Field_diagnostics, field_diagnostics  # noqa: F401
 
 __all__ = [
@@ -23,4 +25,6 @@ __all__ = [
     "ll_compressed_sparse_chol", "ChainContext", "find_ordered_nn", "naive_greedy_coloring",
     "order_maxmin", "Gelman_Rubin_Brooks", "ESS", "get_summary", "summary_columns",
     "Field_diagnostics", "field_diagnostics", "effects_summary", "effects_stats", "mcmc_nngp_predict_response",
+    "POINTWISE_COLUMNS", "pointwise_loglik", "pointwise_loglik_stats", "mcmc_nngp_criteria",
+    "mcmc_nngp_score_response",
 ]

@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "nngp_predict_field", "nngp_predict_stats",
     "nngp_design_set", "nngp_design_mean_stats_chains", "nngp_design_interweave_stats_chains",
     "nngp_design_commit_chains", "nngp_get_mu",
+    "nngp_pointwise_loglik", "nngp_pointwise_loglik_stats",
 )
 SHARD_ID_BYTES = 128  # NNGP_SHARD_ID_BYTES
 IPC_HANDLE_BYTES = 192  # NNGP_IPC_HANDLE_BYTES
@@ -170,6 +171,11 @@ def _load():
     L.nngp_design_interweave_stats_chains.argtypes = [_vp, C.c_int, _dp, _dp, _dp, _dp, _ip]
     L.nngp_design_commit_chains.argtypes = [_vp, C.c_int, _dp, _vp, _vp, _dp, _dp]
     L.nngp_get_mu.argtypes = [_vp, _dp]
+    L.nngp_pointwise_loglik.argtypes = [C.c_int, _vp, C.c_longlong, _vp, _vp, C.c_longlong, C.c_int, _vp,
+                                        C.POINTER(_vp), C.POINTER(C.c_longlong), C.c_int, C.c_longlong, _vp,
+                                        C.c_int, _vp]
+    L.nngp_pointwise_loglik_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong),
+                                              C.POINTER(C.c_int)]
     return L
 
 

@@ -23,6 +23,7 @@
 #include "rec_stream.h"
 #include "summary.h"
 #include "effects.h"
+#include "criteria.h"
 #include "field_diag_run.h"
 #include "predict.h"
 #include "regress.h"
@@ -309,6 +310,7 @@ constexpr int kTileTarget = 2048;  // locations per tile (default tile count: n 
 thread_local std::string g_err;
 thread_local SummaryStats g_summary_stats;  // of this thread's last successful nngp_summary / nngp_summary_probs
 thread_local EffectsStats g_effects_stats;  // of this thread's last successful nngp_effects_summary
+thread_local CriteriaStats g_criteria_stats;  // of this thread's last successful nngp_pointwise_loglik
 thread_local FieldDiagStats g_field_diag_stats;  // of this thread's last successful nngp_field_diag
 thread_local PredictStats g_predict_stats;  // of this thread's last successful nngp_predict_field
 
@@ -3306,6 +3308,28 @@ int nngp_effects_stats(double* copy_ms, double* generate_ms, double* kernel_ms, 
   if (kernel_ms) *kernel_ms = g_effects_stats.kernel_ms;
   if (staged_bytes) *staged_bytes = g_effects_stats.staged_bytes;
   if (chunk_cols) *chunk_cols = g_effects_stats.chunk_cols;
+  return NNGP_OK;
+}
+
+// ---------------------------------------------------------------- pointwise log-likelihood
+int nngp_pointwise_loglik(int device, const double* y, long long n_obs, const int* obs_loc, const double* coef,
+                          long long n_samples, int q, const double* X, const double* const* field_blocks,
+                          const long long* block_rows, int n_blocks, long long n, const double* log_noise_var,
+                          int chunk_cols, double* out) {
+  const CriteriaArgs a{device, y, n_obs, obs_loc, coef, n_samples, q, X, field_blocks, block_rows, n_blocks, n,
+                       log_noise_var, chunk_cols, out};
+  std::string err;
+  const int st = criteria_run(a, &g_criteria_stats, err);
+  return st == NNGP_OK ? NNGP_OK : fail_msg(nullptr, st, err);
+}
+
+int nngp_pointwise_loglik_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols) {
+  if (g_criteria_stats.n_chunks < 1)
+    return fail_msg(nullptr, NNGP_ERR_STATE, "pointwise_loglik_stats: no pointwise_loglik on this thread yet");
+  if (copy_ms) *copy_ms = g_criteria_stats.copy_ms;
+  if (kernel_ms) *kernel_ms = g_criteria_stats.kernel_ms;
+  if (staged_bytes) *staged_bytes = g_criteria_stats.staged_bytes;
+  if (chunk_cols) *chunk_cols = g_criteria_stats.chunk_cols;
   return NNGP_OK;
 }
 

@@ -244,6 +244,170 @@ def effects_stats():
             "chunk_cols": w.value}
 
 
+POINTWISE_COLUMNS = ["fit_mean", "ll_mean", "ll_var", "lppd", "log_cpo", "pit"]
+_HOST_SLAB = 4096  # observations per slab of the host backend's S x slab temporaries
+
+
+def pointwise_loglik(y, obs_loc, field_blocks, log_noise_var, coef=None, X=None, backend="host", device=-1,
+                     chunk_cols=0):
+    """The Gaussian log density of every observation under every saved sample,
+    ll[s, i] = log N(y[i] | field[s, obs_loc[i]] + X[i] . coef[s], exp(log_noise_var[s])),
+    reduced over the samples: an (n_obs, 6) array with POINTWISE_COLUMNS --
+    fit_mean (mean of the means), ll_mean, ll_var (divisor S - 1; NaN for one
+    sample), lppd = log mean exp(ll), log_cpo = -log mean exp(-ll) (both with
+    the maximum taken out first) and pit = mean of Phi((y - mean) / sd).
+
+    ``y`` (n_obs); ``obs_loc`` (n_obs): the 1-based location of each
+    observation, in any order; ``field_blocks``: an S x n array or a list of
+    blocks stacking to S rows (float64 row-contiguous blocks, tail slices of the
+    records included, are passed where they lie); ``log_noise_var`` (S);
+    ``coef`` (S x q) and ``X`` (n_obs x q, rows in the order of ``y``), or
+    neither.  ``backend="host"`` (default) is numpy; ``backend="hip"`` sorts the
+    observations by location (a stable sort), calls nngp_pointwise_loglik on
+    ``device`` (``chunk_cols`` locations staged per launch, 0: automatic) and
+    returns the rows in the caller's order.  A NaN in y[i], X[i] or the
+    location's column gives six NaNs in row i."""
+    if backend not in ("host", "hip"):
+        raise ValueError(f"pointwise_loglik: backend must be 'host' or 'hip', not {backend!r}")
+    y = np.ascontiguousarray(np.asarray(y, np.float64).reshape(-1))
+    loc = np.asarray(obs_loc).reshape(-1)
+    blocks = _row_blocks(field_blocks, "pointwise_loglik")
+    n = blocks[0].shape[1]
+    S = sum(b.shape[0] for b in blocks)
+    lnv = np.ascontiguousarray(np.asarray(log_noise_var, np.float64).reshape(-1))
+    if any(b.shape[1] != n for b in blocks) or lnv.size != S or S < 1:
+        raise ValueError("pointwise_loglik: the field blocks must stack to S x n with one log_noise_var per row")
+    if loc.size != y.size or y.size < 1:
+        raise ValueError("pointwise_loglik: y and obs_loc need one entry per observation")
+    if loc.min() < 1 or loc.max() > n:
+        raise ValueError("pointwise_loglik: obs_loc must lie in 1 .. n")
+    if (coef is None) != (X is None):
+        raise ValueError("pointwise_loglik: coef and X go together")
+    if coef is not None:
+        coef, X = np.asarray(coef, np.float64), np.asarray(X, np.float64)
+        if coef.ndim != 2 or X.ndim != 2 or coef.shape != (S, X.shape[1]) or X.shape[0] != y.size:
+            raise ValueError("pointwise_loglik: coef must be S x q and X n_obs x q")
+        if coef.shape[1] == 0:
+            coef = X = None
+    if not np.all(np.isfinite(lnv)):
+        raise ValueError("pointwise_loglik: log_noise_var must be finite")
+    if backend == "hip":
+        return _pointwise_hip(y, loc, blocks, lnv, coef, X, device, chunk_cols)
+    a = -0.5 * (np.log(2.0 * np.pi) + lnv)[:, None]
+    h = (0.5 * np.exp(-lnv))[:, None]
+    g = np.sqrt(2.0 * h)
+    from scipy.special import erfc
+
+    out = np.empty((y.size, 6))
+    col = loc.astype(np.int64) - 1
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for i0 in range(0, y.size, _HOST_SLAB):
+            sl = slice(i0, i0 + _HOST_SLAB)
+            mean = np.vstack([b[:, col[sl]] for b in blocks])
+            if coef is not None:
+                # column by column, the order of the device's chain (a BLAS product
+                # may round equal rows differently)
+                acc = coef[:, :1] * X[sl, 0]
+                for k in range(1, coef.shape[1]):
+                    acc += coef[:, k:k + 1] * X[sl, k]
+                mean = mean + acc
+            r = y[sl] - mean
+            ll = a - h * r * r
+            M, Mn = np.fmax.reduce(ll, axis=0), np.fmax.reduce(-ll, axis=0)
+            o = out[sl]
+            o[:, 0] = mean.sum(0) / S
+            o[:, 1] = ll.sum(0) / S
+            o[:, 2] = ((ll - o[:, 1]) ** 2).sum(0) / (S - 1) if S > 1 else np.nan
+            o[:, 3] = M + np.log(np.exp(ll - M).sum(0)) - np.log(S)
+            o[:, 4] = -(Mn + np.log(np.exp(-ll - Mn).sum(0)) - np.log(S))
+            o[:, 5] = (0.5 * erfc(-(r * g) * np.sqrt(0.5))).sum(0) / S
+            o[np.isnan(o[:, 1])] = np.nan
+    return out
+
+
+def _pointwise_hip(y, loc, blocks, lnv, coef, X, device, chunk_cols):
+    import ctypes as C
+
+    from . import _lib
+
+    # observations that come sorted already are passed as they are (an X whose
+    # transpose is C-contiguous where it lies: no n_obs x q gather or copy)
+    is_sorted = bool(np.all(loc[1:] >= loc[:-1]))
+    order = slice(None) if is_sorted else np.argsort(loc, kind="stable")
+    ys, ls = np.ascontiguousarray(y[order]), np.ascontiguousarray(loc[order], np.int32)
+    q = 0 if coef is None else coef.shape[1]
+    coef_cm = None if q == 0 else _lib.colmajor(coef, np.float64)
+    X_cm = None if q == 0 else _lib.colmajor(X if is_sorted else X[order], np.float64)
+    rows = (C.c_longlong * len(blocks))(*[b.shape[0] for b in blocks])
+    ptrs = (C.c_void_p * len(blocks))(*[b.ctypes.data for b in blocks])
+    out = np.empty((6, y.size))  # n_obs x 6 column-major
+    _lib.check(_lib.lib.nngp_pointwise_loglik(
+        int(device), ys.ctypes.data, y.size, ls.ctypes.data, None if q == 0 else coef_cm.ctypes.data, lnv.size, q,
+        None if q == 0 else X_cm.ctypes.data, ptrs, rows, len(blocks), blocks[0].shape[1], lnv.ctypes.data,
+        int(chunk_cols), out.ctypes.data))
+    res = np.empty((y.size, 6))
+    res[order] = out.T
+    return res
+
+
+def pointwise_loglik_stats():
+    """HIP-event times and staging size of this thread's last device
+    pointwise_loglik (nngp_pointwise_loglik_stats)."""
+    import ctypes as C
+
+    from . import _lib
+
+    cp, kn, by, w = C.c_double(), C.c_double(), C.c_longlong(), C.c_int()
+    _lib.check(_lib.lib.nngp_pointwise_loglik_stats(C.byref(cp), C.byref(kn), C.byref(by), C.byref(w)))
+    return {"copy_ms": cp.value, "kernel_ms": kn.value, "staged_bytes": by.value, "chunk_cols": w.value}
+
+
+def mcmc_nngp_criteria(mcmc_nngp_list, burn_in=0.5, backend="host", device=-1):
+    """WAIC, LPML and DIC of a fit from the pointwise log-likelihood of its
+    stored field samples (pointwise_loglik over the chains' stack).
+
+    The stored iterations are predict.py's: saved_field > burn_in * max.  Per
+    chain the tail of params["field"] is one block, read where it lies; the
+    field holds beta_0, so the mean of observation i is
+    field[locs_match[i]] + X[i] . beta with the centred X["X"] (no regression
+    term without covariates).  Returns ``pointwise`` (n_obs x 6, ``columns``),
+    ``lppd`` and ``p_waic`` (the sums of lppd and ll_var), ``waic`` =
+    -2 (lppd - p_waic), ``lpml`` (the sum of log_cpo), ``dbar`` =
+    -2 sum ll_mean, ``dhat`` = -2 sum log N(y | fit_mean, exp(mean
+    log_noise_var)), ``p_dic`` = dbar - dhat, ``dic`` = dbar + p_dic and
+    ``n_samples``."""
+    L = mcmc_nngp_list
+    recs = list(L["records"].values())
+    saved = np.asarray(recs[0]["saved_field"])
+    sel = saved > burn_in * saved.max()
+    idx = np.nonzero(sel)[0]
+    if idx.size == 0:
+        raise ValueError("mcmc_nngp_criteria: no stored field sample after burn-in")
+    stored = saved[sel].astype(int)
+    suffix = idx[0] + idx.size == sel.size
+    blocks, coef, lnv = [], [], []
+    has_beta = L["X"].get("X") is not None and all("beta" in c["params"] for c in recs)
+    for c in recs:
+        f = c["params"]["field"]
+        blocks.append(f[idx[0]:] if suffix and f.shape[0] == sel.size else f[sel])
+        lnv.append(np.asarray(c["params"]["log_noise_variance"], np.float64).reshape(-1)[stored - 1])
+        if has_beta:
+            coef.append(np.asarray(c["params"]["beta"], np.float64)[stored - 1])
+    lnv = np.concatenate(lnv)
+    y = np.asarray(L["observed_field"], np.float64)
+    pw = pointwise_loglik(y, L["vecchia_approx"]["locs_match"], blocks, lnv,
+                          coef=np.vstack(coef) if has_beta else None, X=L["X"]["X"] if has_beta else None,
+                          backend=backend, device=device)
+    lppd, p_waic, lpml = pw[:, 3].sum(), pw[:, 2].sum(), pw[:, 4].sum()
+    dbar = -2.0 * pw[:, 1].sum()
+    lnv_bar = lnv.mean()
+    dhat = -2.0 * (-0.5 * (np.log(2.0 * np.pi) + lnv_bar) - 0.5 * np.exp(-lnv_bar) * (y - pw[:, 0]) ** 2).sum()
+    p_dic = dbar - dhat
+    return {"pointwise": pw, "columns": list(POINTWISE_COLUMNS), "lppd": lppd, "p_waic": p_waic,
+            "waic": -2.0 * (lppd - p_waic), "lpml": lpml, "dbar": dbar, "dhat": dhat, "p_dic": p_dic,
+            "dic": dbar + p_dic, "n_samples": int(lnv.size)}
+
+
 def _plogis(x):
     return 1 / (1 + np.exp(-x))
 

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from .context import ChainContext
-from .estimate import effects_summary, get_summary, summary_columns
+from .estimate import POINTWISE_COLUMNS, effects_summary, get_summary, pointwise_loglik, summary_columns
 from .graph import find_ordered_nn, naive_greedy_coloring
 from .model import covparms
 
@@ -312,3 +312,40 @@ def mcmc_nngp_predict_response(mcmc_nngp_list, predicted_locs, X_predicted, burn
     return {"predicted_locs": field["predicted_locs"], "predicted_response_summary": summary,
             "predicted_response_summary_columns": summary_columns(summary_probs, summary_thresholds),
             "field_prediction": field}
+
+
+def mcmc_nngp_score_response(mcmc_nngp_list, predicted_locs, X_predicted, y_new, burn_in=0.5, m=10, seed=1,
+                             backend="hip", device=-1, **predict_field_kw):
+    """Scores of held-out observations ``y_new`` at ``predicted_locs`` (one per
+    location): the held-out counterpart of mcmc_nngp_criteria.
+
+    The field samples come from mcmc_nngp_predict_field(engine="batched") as in
+    mcmc_nngp_predict_response (field - beta_0; ``m``, ``seed``, ``device`` and
+    ``predict_field_kw`` go there), the regression term is the de-centred
+    cbind(beta_0, beta) row against cbind(1, X_predicted), the noise variance
+    that iteration's exp(log_noise_variance); pointwise_loglik(``backend``)
+    reduces them with the per-chain field arrays as its blocks, read where they
+    lie.  Returns ``pointwise`` (n_pred x 6, ``columns``), ``log_score`` (the
+    mean of lppd), ``rmse`` of fit_mean, ``pit``, ``coverage_95`` (the share of
+    pit in [0.025, 0.975]) and the field prediction's own dict."""
+    if backend not in ("host", "hip"):
+        raise ValueError(f"mcmc_nngp_score_response: backend must be 'host' or 'hip', not {backend!r}")
+    L = mcmc_nngp_list
+    predict_field_kw.setdefault("summary_backend", backend)
+    field = mcmc_nngp_predict_field(L, predicted_locs, burn_in=burn_in, m=m, seed=seed, device=device,
+                                    engine="batched", **predict_field_kw)
+    n_pred = field["predicted_locs"].shape[0]
+    y_new = np.asarray(y_new, np.float64).reshape(-1)
+    if y_new.size != n_pred:
+        raise ValueError("mcmc_nngp_score_response: y_new needs one value per predicted location")
+    if X_predicted is None:
+        X_predicted = np.zeros((n_pred, 0))
+    mm, coef, stored = _stored_coef(L, X_predicted, burn_in, True, True)
+    lnv = np.concatenate([np.asarray(c["params"]["log_noise_variance"], np.float64).reshape(-1)[stored - 1]
+                          for c in L["records"].values()])
+    pw = pointwise_loglik(y_new, np.arange(1, n_pred + 1), field["predicted_field_samples"], lnv,
+                          coef=np.vstack(coef), X=mm, backend=backend, device=device)
+    pit = pw[:, 5]
+    return {"predicted_locs": field["predicted_locs"], "pointwise": pw, "columns": list(POINTWISE_COLUMNS),
+            "log_score": float(pw[:, 3].mean()), "rmse": float(np.sqrt(np.mean((y_new - pw[:, 0]) ** 2))),
+            "pit": pit, "coverage_95": float(np.mean((pit >= 0.025) & (pit <= 0.975))), "field_prediction": field}

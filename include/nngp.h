@@ -43,6 +43,8 @@
  *   nngp_summary_probs ....... the same with chosen quantiles and exceedance probabilities
  *   nngp_effects_summary ..... beta_matrix[, subset] %*% t(X_pred) and its get_summary,
  *                              Scripts/mcmc_nngp_predict.R:92-102, the samples generated on the device
+ *   nngp_pointwise_loglik .... the dnorm terms of update_Gaussian.R:130-131,281 per saved sample
+ *                              and observation, reduced to WAIC / LPML / DIC / PIT ingredients
  *   nngp_field_diag .......... Individual_PSRF of Gelman_Rubin_Brooks and ESS,
  *                              Scripts/mcmc_nngp_diagnose.R:1-24,107-118, per field location
  *   nngp_predict_field ....... the per-sample body of mcmc_nngp_predict_field,
@@ -67,7 +69,7 @@
 extern "C" {
 #endif
 
-#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_probs, nngp_summary_stats, nngp_effects_summary, nngp_effects_stats, nngp_field_diag, nngp_field_diag_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
+#define NNGP_ABI_VERSION 14  /* 14: nngp_tri_rescues (+ nngp_summary, nngp_summary_probs, nngp_summary_stats, nngp_effects_summary, nngp_effects_stats, nngp_field_diag, nngp_field_diag_stats, nngp_predict_field, nngp_predict_stats, nngp_design_set, nngp_design_mean_stats_chains, nngp_design_interweave_stats_chains, nngp_design_commit_chains, nngp_get_mu, nngp_pointwise_loglik, nngp_pointwise_loglik_stats: additive, same version); 13: nngp_records_stream; 12: nngp_info gained tile_rows_needed, device_lds */
 #define NNGP_SHARD_ID_BYTES 128 /* RCCL unique id */
 #define NNGP_IPC_HANDLE_BYTES 192 /* HIP IPC handles of a tile shard's granule buffer, w replica, flags */
 
@@ -512,6 +514,67 @@ int nngp_effects_summary(int device, const double* coef, long long n_samples, in
  * be NULL.  NNGP_ERR_STATE: none yet. */
 int nngp_effects_stats(double* copy_ms, double* generate_ms, double* kernel_ms,
                        long long* staged_bytes, int* chunk_cols);
+
+/* ---------- pointwise log-likelihood of the saved samples, reduced per observation (no context) ---------- */
+/* The Gaussian log density of every observation under every saved sample (the
+ * dnorm terms of Scripts/mcmc_nngp_update_Gaussian.R:130-131,281), reduced over
+ * the samples on the device: what WAIC, LPML, DIC and the log score / PIT of
+ * held-out observations are sums of.  The n_samples x n_obs matrix exists nowhere.
+ * y (n_obs) and obs_loc (n_obs: the 1-based location of each observation,
+ * non-decreasing -- the order of vecchia_approx$hctam_scol; a location may carry
+ * 0, 1 or many observations).  coef: n_samples x q column-major; X: n_obs x q
+ * column-major, rows in the order of y; q == 0 with both NULL: no regression
+ * term.  field_blocks: the row-wise stack of n_blocks host blocks (nngp_summary's
+ * convention: block k is block_rows[k] x n row-major, pitch n, read where it
+ * lies).  log_noise_var: n_samples.
+ * Per sample s, a_s = -0.5 (log(2 pi) + lnv_s), h_s = 0.5 exp(-lnv_s) and
+ * g_s = sqrt(2 h_s) are computed once on the host in fp64.  The value of sample
+ * s at observation i (c = obs_loc[i] - 1) is defined by its arithmetic, in this
+ * order:
+ *   acc  = coef[s,0] * X[i,0]
+ *   acc  = fma(coef[s,k], X[i,k], acc)     k = 1 .. q-1, in column order
+ *   mean = field[s,c] + acc                (field[s,c] alone when q == 0)
+ *   r    = y[i] - mean
+ *   ll   = fma(-(h_s * r), r, a_s)
+ *   p    = 0.5 * erfc(-((r * g_s) * C))    C = the double nearest 1 / sqrt(2)
+ * out: n_obs x 6 column-major; every sum below runs over s in row order, in
+ * fp64, one addition per sample (D = (double)n_samples):
+ *   1 fit_mean = (sum mean) / D
+ *   2 ll_mean  = (sum ll) / D
+ *   3 ll_var   = (sum by ss = fma(d, d, ss), d = ll - ll_mean) / (D - 1); NaN for n_samples == 1
+ *   4 lppd     = (M + log(sum exp(ll - M))) - log(D),       M  = max_s ll
+ *   5 log_cpo  = -((M' + log(sum exp(-ll - M'))) - log(D)), M' = max_s (-ll)
+ *   6 pit      = (sum p) / D
+ * (log(D) from the host).  The maxima shift the sums, so lppd and log_cpo are
+ * finite whenever every ll is.  An observation's six numbers depend on its own
+ * y, X row, and its location's column alone: not on n, n_obs, the chunking, its
+ * position or the other observations.  A NaN in y[i], X[i, ] or the location's
+ * column gives six NaNs for observation i and for no other (a NaN coef poisons
+ * every observation).
+ * Staging as nngp_summary: column chunks of chunk_cols locations (0 = automatic:
+ * both chunk buffers within 1 GiB, never below 64 columns) go through two device
+ * buffers, the copy of one chunk running beside the kernel of the chunk before;
+ * a chunk no observation reads is not staged.  y, obs_loc, coef, X and the
+ * per-sample constants are copied once, out is held on the device and copied
+ * out once.  device: HIP ordinal (-1: current); the calling thread's current
+ * device is the same after the call as before it.
+ * NNGP_ERR_ARG (before any HIP call): a null y, obs_loc, out or log_noise_var;
+ * n_obs < 1; n < 1; n_samples outside 1..2^31-1; q outside 0..1024; q > 0 with a
+ * null coef or X; an obs_loc that decreases or lies outside 1..n; no blocks, a
+ * null block, or block rows that do not sum to n_samples; a NaN or infinite
+ * log_noise_var; chunk_cols < 0. */
+int nngp_pointwise_loglik(int device,
+                          const double* y, long long n_obs, const int* obs_loc,
+                          const double* coef, long long n_samples, int q,
+                          const double* X,
+                          const double* const* field_blocks, const long long* block_rows, int n_blocks, long long n,
+                          const double* log_noise_var,
+                          int chunk_cols, double* out);
+/* Measurement, as nngp_summary_stats: the calling thread's last successful
+ * nngp_pointwise_loglik -- HIP-event times of the field copies and of the
+ * kernels (each summed over the chunks), the bytes staged and the chunk width
+ * used.  Any pointer may be NULL.  NNGP_ERR_STATE: none yet. */
+int nngp_pointwise_loglik_stats(double* copy_ms, double* kernel_ms, long long* staged_bytes, int* chunk_cols);
 
 /* ---------- convergence diagnostics per field location (no context) ---------- */
 /* Individual_PSRF of Gelman_Rubin_Brooks and ESS (Scripts/mcmc_nngp_diagnose.R:1-24,

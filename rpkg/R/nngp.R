@@ -134,6 +134,26 @@ nngp_effects_summary <- function(coef, X, addend = NULL, noise_sd = NULL, seed =
 }
 # HIP-event times (ms), staged bytes and chunk width of the last nngp_effects_summary
 nngp_effects_stats <- function() .Call(C_nngp_effects_stats)
+# The Gaussian log density of every observation under every saved sample (the dnorm terms of
+# Scripts/mcmc_nngp_update_Gaussian.R:130-131,281), reduced over the samples on the device: y (n_obs), obs_loc
+# (n_obs, the 1-based location of each observation, any order: vecchia_approx$locs_match), field S x n (the saved
+# field rows, beta_0 included), log_noise_var (S), coef NULL or S x q with X n_obs x q.  -> n_obs x 6 with columns
+# fit_mean, ll_mean, ll_var, lppd, log_cpo, pit, rows in the caller's order (WAIC = -2 (sum(lppd) - sum(ll_var)),
+# LPML = sum(log_cpo))
+nngp_pointwise_loglik <- function(y, obs_loc, field, log_noise_var, coef = NULL, X = NULL, device = -1L) {
+  ord <- order(obs_loc)  # stable: ties keep the caller's order
+  if (!is.null(coef)) {
+    coef <- as.matrix(coef) + 0
+    X <- (as.matrix(X) + 0)[ord, , drop = FALSE]
+  }
+  out <- .Call(C_nngp_pointwise_loglik, as.integer(device), as.double(y)[ord], as.integer(obs_loc)[ord], coef,
+               if (is.null(coef)) NULL else X, t(field) + 0, as.double(log_noise_var))
+  out[ord, ] <- out
+  colnames(out) <- c("fit_mean", "ll_mean", "ll_var", "lppd", "log_cpo", "pit")
+  out
+}
+# HIP-event times (ms), staged bytes and chunk width of the last nngp_pointwise_loglik
+nngp_pointwise_loglik_stats <- function() .Call(C_nngp_pointwise_loglik_stats)
 # R-hat (Individual_PSRF of Gelman_Rubin_Brooks, n := saved rows) and effective sample size (ESS) of every
 # field location (Scripts/mcmc_nngp_diagnose.R:1-24,107-118) on the device.  chains: a list with one
 # samples x locations matrix per chain (the saved field rows after burn-in, centred); -> n x 5 with

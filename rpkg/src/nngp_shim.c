@@ -567,6 +567,60 @@ SEXP C_nngp_effects_stats(void) {
   return out;
 }
 
+/* The pointwise Gaussian log-likelihood of the saved samples reduced per
+ * observation (nngp_pointwise_loglik; the dnorm terms of
+ * update_Gaussian.R:130-131,281): y (n_obs) and obs_loc (n_obs integers,
+ * 1-based, non-decreasing: the R wrapper sorts); coef NULL or S x q with X
+ * n_obs x q as R holds them; field_t n x S, the TRANSPOSE of the S x n field
+ * samples, so that R's column-major storage is the S row-major rows of n the
+ * library reads where they lie; log_noise_var S values.  -> n_obs x 6; the R
+ * wrapper names the columns and restores the caller's order. */
+SEXP C_nngp_pointwise_loglik(SEXP device, SEXP y, SEXP obs_loc, SEXP coef, SEXP X, SEXP field_t, SEXP log_noise_var) {
+  if (TYPEOF(y) != REALSXP || TYPEOF(obs_loc) != INTSXP || XLENGTH(y) != XLENGTH(obs_loc) || XLENGTH(y) < 1)
+    Rf_error("nngp: pointwise_loglik: y must be numeric and obs_loc integer, of one length");
+  if (TYPEOF(field_t) != REALSXP || !Rf_isMatrix(field_t) || TYPEOF(log_noise_var) != REALSXP)
+    Rf_error("nngp: pointwise_loglik: the field must be a numeric matrix and log_noise_var numeric");
+  const long long n_obs = (long long)XLENGTH(y);
+  const int n = Rf_nrows(field_t), S = Rf_ncols(field_t);
+  if (XLENGTH(log_noise_var) != S) Rf_error("nngp: pointwise_loglik: log_noise_var needs one value per sample");
+  const int has_q = TYPEOF(coef) != NILSXP;
+  int q = 0;
+  if (has_q) {
+    if (TYPEOF(coef) != REALSXP || !Rf_isMatrix(coef) || TYPEOF(X) != REALSXP || !Rf_isMatrix(X))
+      Rf_error("nngp: pointwise_loglik: coef and X must be numeric matrices");
+    q = Rf_ncols(coef);
+    if (Rf_nrows(coef) != S || Rf_ncols(X) != q || Rf_nrows(X) != n_obs)
+      Rf_error("nngp: pointwise_loglik: coef must be S x q and X n_obs x q");
+  }
+  const double* block = REAL(field_t);
+  const long long block_rows = S;
+  SEXP out = PROTECT(Rf_allocMatrix(REALSXP, (int)n_obs, 6));
+  check(nngp_pointwise_loglik(as_int(device), REAL(y), n_obs, INTEGER(obs_loc), q ? REAL(coef) : NULL, S, q,
+                              q ? REAL(X) : NULL, &block, &block_rows, 1, n, REAL(log_noise_var), 0, REAL(out)),
+        NULL);
+  UNPROTECT(1);
+  return out;
+}
+
+/* the last pointwise log-likelihood's HIP-event times (ms), staged bytes and chunk width */
+SEXP C_nngp_pointwise_loglik_stats(void) {
+  static const char* names[4] = {"copy_ms", "kernel_ms", "staged_bytes", "chunk_cols"};
+  double v[2] = {0, 0};
+  long long bytes = 0;
+  int cols = 0;
+  check(nngp_pointwise_loglik_stats(&v[0], &v[1], &bytes, &cols), NULL);
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, 4));
+  SEXP nm = PROTECT(Rf_allocVector(STRSXP, 4));
+  REAL(out)[0] = v[0];
+  REAL(out)[1] = v[1];
+  REAL(out)[2] = (double)bytes;
+  REAL(out)[3] = (double)cols;
+  for (int i = 0; i < 4; ++i) SET_STRING_ELT(nm, i, Rf_mkChar(names[i]));
+  Rf_setAttrib(out, R_NamesSymbol, nm);
+  UNPROTECT(2);
+  return out;
+}
+
 /* Per-location R-hat and effective sample size of the field samples
  * (Scripts/mcmc_nngp_diagnose.R:1-24,107-118).  chains_t: a list with one
  * n x S numeric matrix per chain, the TRANSPOSE of its S saved rows x n
@@ -1041,6 +1095,8 @@ static const R_CallMethodDef call_methods[] = {
     E(C_nngp_summary_stats, 0),
     E(C_nngp_effects_summary, 9),
     E(C_nngp_effects_stats, 0),
+    E(C_nngp_pointwise_loglik, 7),
+    E(C_nngp_pointwise_loglik_stats, 0),
     E(C_nngp_field_diag, 2),
     E(C_nngp_field_diag_stats, 0),
     E(C_nngp_predict_field, 14),
